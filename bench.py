@@ -14,6 +14,11 @@ inversions alone. The RCCL all-gather over xGMI that reassembles the result on e
 has) is timed separately and reported as `allgather_ms` / `allgather_GBs` beside the per-link xGMI bound; it is not in
 `value`. `--batch B` instead gives every rank B matrices (weak scaling).
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line. `--full` adds everything else: the measured
+copy bandwidth, the info-code and residual checks of the timed output, the other single-GPU workloads, the end-to-end host-pointer
+call, the mixed workload's short runs, the per-bin and host-side figures of `--workload mixed`, and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of it) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -81,6 +86,26 @@ def make_spd(n, batch, seed, device, dtype=torch.float64):
 def make_general(n, batch, seed, device, dtype=torch.float64):
     g = torch.Generator(device=device).manual_seed(seed)
     return torch.rand((batch * n * n,), generator=g, dtype=dtype, device=device)
+
+
+DUMP_BYTES = 48 << 20  # the matrices written by --dump-outputs (the whole dump stays below 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each CPU array as out_dir/<name>.npy (float32 / float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr)
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
+def sample_rows(count, row_bytes):
+    """Sorted indices of a fixed, seeded sample of `count` rows that fits in DUMP_BYTES (every row when they all fit)."""
+    k = min(count, max(1, DUMP_BYTES // row_bytes))
+    if k == count:
+        return np.arange(count)
+    return np.sort(np.random.default_rng(20240917).choice(count, k, replace=False))
 
 
 def usable_cores():
@@ -236,7 +261,7 @@ def mixed_result(args, api, device, rank, world):
     host_s[0] = 0.0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if multi:
         tdist.barrier()
@@ -247,6 +272,20 @@ def mixed_result(args, api, device, rank, world):
         t = torch.tensor([elapsed], dtype=torch.float64, device=backend_dev)
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         elapsed = float(t[0].item())
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        # the means of the last timed flush, in submission order (chunk by chunk as `table` lists them)
+        dump_outputs(args.dump_outputs, {"means": last.cpu().numpy()})
+    total = sum(mix.values()) * world * args.steps
+    out = {
+        "metric": "pipeline items/s (mixed sizes)", "value": total / elapsed, "unit": "items/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "mixed: fp32 mean pipeline, size-binned queues 32/128/512/1024 (BASELINE configs[4])",
+                   "mix_items_per_step_per_gpu": mix, "queue": "C (matinv_queue_*, csrc/queue.hip)", "flushes_in_flight": inflight,
+                   "stream_placement": placement,
+                   "includes": "submit of same-size chunks of <= 256 items (sizes interleaved) + flush: segmented gather + one fused launch per size, one stream per bin"}}
+    if not getattr(args, "full", True):
+        return out
     # host work of one step by itself: submit + flush timed with the device idle (in the timed loop above the host runs ahead
     # of the device and then waits inside flush for the previous step's results, so its share there is not host WORK)
     idle = []
@@ -277,19 +316,11 @@ def mixed_result(args, api, device, rank, world):
     # the flushed means against the per-bin launches of the same items (the queue adds gather / scatter only)
     means = step()
     torch.cuda.synchronize()
-    total = sum(mix.values()) * world * args.steps
-    return {
-        "metric": "pipeline items/s (mixed sizes)", "value": total / elapsed, "unit": "items/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "mixed: fp32 mean pipeline, size-binned queues 32/128/512/1024 (BASELINE configs[4])",
-                   "mix_items_per_step_per_gpu": mix, "queue": "C (matinv_queue_*, csrc/queue.hip)", "flushes_in_flight": inflight,
-                   "stream_placement": placement,
-                   "includes": "submit of same-size chunks of <= 256 items (sizes interleaved) + flush: segmented gather + one fused launch per size, one stream per bin"},
-        "host_ms_per_step": host_idle_ms, "host_share": host_idle_ms / (elapsed / args.steps * 1e3),
-        "host_ms_in_calls_back_to_back": host_s[0] / args.steps * 1e3,
-        "means_finite": bool(torch.isfinite(means).all()),
-        "per_bin": per_bin}
+    out.update({"host_ms_per_step": host_idle_ms, "host_share": host_idle_ms / (elapsed / args.steps * 1e3),
+                "host_ms_in_calls_back_to_back": host_s[0] / args.steps * 1e3,
+                "means_finite": bool(torch.isfinite(means).all()),
+                "per_bin": per_bin})
+    return out
 
 
 def run_mixed(args, api, device, rank, world):
@@ -379,9 +410,15 @@ def main():
                                                              "with --gpus N > 1 the shard of --total-batch)")
     ap.add_argument("--total-batch", type=int, default=1_000_000, help="N > 1: matrices over ALL GPUs (BASELINE configs[3])")
     ap.add_argument("--kernel", default="auto", choices=["auto", "lds", "rowlane", "tile", "tilep", "row", "blocked"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the short runs of the other single-GPU workloads")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure "
+                                                         "(see the module docstring); off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-others", action="store_true", help="--full: skip the short runs of the other single-GPU workloads")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the timed all-gather of the results")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy: inverse (matrices x n*n, each "
+                         "matrix column-major as returned) and info (as float) for a fixed, seeded sample of rank 0's batch of at "
+                         "most 48 MB; means (float32, every item) for --workload mixed")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -415,7 +452,7 @@ def main():
     api = importlib.import_module(PKG + ".api")
     shard = importlib.import_module(PKG + ".shard")
     # the queues of the mixed-size workload first: where their streams land among the hardware queues is decided when they are created
-    mixed_queues = make_mixed_queues(device, 4) if (args.workload == "mixed" or (world == 1 and not args.no_others)) else []
+    mixed_queues = make_mixed_queues(device, 4) if (args.workload == "mixed" or (args.full and world == 1 and not args.no_others)) else []
     if args.workload == "mixed":
         args.queues = mixed_queues
         run_mixed(args, api, device, rank, world)
@@ -453,7 +490,8 @@ def main():
     # what a plain device-to-device copy of the same bytes reaches on this box (SURVEY 8d asks for the fraction against
     # the measured copy bandwidth beside the nominal 8 TB/s); torch's copy kernel, same read+write byte count. Measured
     # before the timed region: it belongs to the set-up, and the card has then left its idle clocks when the steps start
-    # (no host synchronisation between these copies and the warm-up steps: the events are read after the timed region)
+    # (no host synchronisation between these copies and the warm-up steps: the events are read after the timed region).
+    # The copies run in a plain run too, as the clock warm-up the headline has always had; only --full reads their events
     x.copy_(a)
     copy_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(9)]
     for s_, e_ in copy_ev:
@@ -483,8 +521,15 @@ def main():
     elapsed = time.perf_counter() - t0
     step_ms = [s.elapsed_time(e) for s, e in ev]
     kern_ms = float(np.mean(step_ms))
-    assert int(info[:batch].abs().sum()) == 0, "synthetic batch reported singular matrices"
-    copy_gbs = 2 * a.numel() * a.element_size() / (float(np.median([s_.elapsed_time(e_) for s_, e_ in copy_ev])) * 1e-3) / 1e9
+    if args.dump_outputs and rank == 0:
+        idx = sample_rows(batch, n * n * x.element_size())
+        sel = torch.from_numpy(idx).to(device)
+        dump_outputs(args.dump_outputs, {"inverse": x.view(batch, n * n)[sel].cpu().numpy(),
+                                         "info": info[:batch][sel].to(torch.float32).cpu().numpy()})
+    copy_gbs = None
+    if args.full:
+        assert int(info[:batch].abs().sum()) == 0, "synthetic batch reported singular matrices"
+        copy_gbs = 2 * a.numel() * a.element_size() / (float(np.median([s_.elapsed_time(e_) for s_, e_ in copy_ev])) * 1e-3) / 1e9
 
     gather = None
     if dist is not None:
@@ -526,14 +571,15 @@ def main():
         gather["n_ranks_seen"] = ranks_seen
 
     # quick correctness guard on the timed output (not timed): residual of a few matrices
-    am = a.view(batch, n, n)[:8]
-    xm = x.view(batch, n, n)[:8]
-    resid = float((torch.bmm(am, xm) - torch.eye(n, dtype=a.dtype, device=device)).abs().max())
-    if os.environ.get("MATINV_BENCH_NO_RESIDUAL") != "1":  # (profiling builds that move the bytes without inverting)
-        assert resid < (1e-9 if general else 1e-11) * n, f"residual {resid}"
+    if args.full:
+        am = a.view(batch, n, n)[:8]
+        xm = x.view(batch, n, n)[:8]
+        resid = float((torch.bmm(am, xm) - torch.eye(n, dtype=a.dtype, device=device)).abs().max())
+        if os.environ.get("MATINV_BENCH_NO_RESIDUAL") != "1":  # (profiling builds that move the bytes without inverting)
+            assert resid < (1e-9 if general else 1e-11) * n, f"residual {resid}"
 
     others, end_to_end, mixed = {}, None, None
-    if rank == 0 and world == 1 and not args.no_others:
+    if args.full and rank == 0 and world == 1 and not args.no_others:
         # the other single-GPU workloads, a few launches each (same timing method), so that every path -- the weak ones
         # included -- is driver-timed AND residual-checked each round
         del a, x
@@ -677,8 +723,9 @@ def main():
         hbm_side = roof if roof["bound"] == "hbm" else roof_other
         hbm_side["guide_copy_GBs"] = HBM_GUIDE_ACHIEVABLE_GBS
         hbm_side["frac_of_guide_copy"] = hbm_side["achieved"] / HBM_GUIDE_ACHIEVABLE_GBS
-        hbm_side["measured_copy_GBs"] = copy_gbs
-        hbm_side["frac_of_measured_copy"] = hbm_side["achieved"] / copy_gbs
+        if copy_gbs is not None:
+            hbm_side["measured_copy_GBs"] = copy_gbs
+            hbm_side["frac_of_measured_copy"] = hbm_side["achieved"] / copy_gbs
         if roof_other is not None:
             roof["other_bound"] = roof_other
         out = {
@@ -702,7 +749,7 @@ def main():
             out["end_to_end"] = end_to_end
         if mixed is not None:
             out["mixed"] = mixed
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(n, algo_name)
         print(json.dumps(out), flush=True)
     if dist is not None:

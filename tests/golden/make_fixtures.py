@@ -83,6 +83,21 @@ def main():
         gold[f"{d}/variances"] = oracle.variance_batched(r["a"][0], r["b"][0], r["c"][0], r["e"][0], n)
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "oracle_fp64.npz"), **gold)
     print("oracle_fp64.npz:", len(gold), "arrays")
+    ref_cholesky_4x4()
+
+
+def ref_cholesky_4x4():
+    """ref_cholesky_4x4.npz: what the reference's scalar Cholesky binary (oracle/_ref/inverse_cholesky_cpu) prints for the six
+    4x4 matrices of tests/test_oracle.py::test_against_reference_binary_4x4, so that the test also runs where it cannot be built."""
+    rng = np.random.default_rng(7)
+    mats4 = [np.array([[18, 22, 54, 42], [22, 70, 86, 62], [54, 86, 174, 134], [42, 62, 134, 106]], dtype=np.float64)]
+    for _ in range(5):
+        r = rng.random((4, 4))
+        mats4.append(r + r.T + 4 * np.eye(4))
+    outs = [oracle.ref_cholesky_4x4(a) for a in mats4]
+    assert all(o is not None for o in outs), "oracle/_ref/inverse_cholesky_cpu is not built"
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "ref_cholesky_4x4.npz"), a=np.stack(mats4), inv=np.stack(outs))
+    print("ref_cholesky_4x4.npz:", len(mats4), "matrices")
 
 
 if __name__ == "__main__":

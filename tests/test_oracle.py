@@ -55,17 +55,21 @@ def test_reference_simplemean_cholesky():
 
 def test_against_reference_binary_4x4():
     """oracle/_ref/inverse_cholesky_cpu is /root/reference/src/inverse_cholesky_cpu.c compiled unmodified
-    (fp32, N=4). Its output must match the fp32 restatement to fp32 round-off and the fp64 one to ~cond*eps32."""
+    (fp32, N=4). Its output must match the fp32 restatement to fp32 round-off and the fp64 one to ~cond*eps32.
+    The binary's output for these six matrices is stored (tests/golden/ref_cholesky_4x4.npz, make_fixtures.py); where the
+    binary is built it must still print exactly that."""
     rng = np.random.default_rng(7)
     mats4 = [np.array([[18, 22, 54, 42], [22, 70, 86, 62], [54, 86, 174, 134], [42, 62, 134, 106]], dtype=np.float64)]
     for _ in range(5):
         r = rng.random((4, 4))
         mats4.append(r + r.T + 4 * np.eye(4))
+    stored = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_cholesky_4x4.npz"))
+    assert np.array_equal(stored["a"], np.stack(mats4))
     ran = 0
-    for a in mats4:
-        ref = oracle.ref_cholesky_4x4(a)
-        if ref is None:
-            pytest.skip("oracle/_ref not built (reference mount absent and no prebuilt binary)")
+    for a, ref in zip(mats4, stored["inv"]):
+        live = oracle.ref_cholesky_4x4(a)
+        if live is not None:
+            assert np.array_equal(live, ref)
         ran += 1
         flat = np.ascontiguousarray(a.T).reshape(-1)
         inv32, _ = oracle.inverse_batched(flat.astype(np.float32), 4, oracle.ALGO_CHOLESKY)

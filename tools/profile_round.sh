@@ -10,12 +10,12 @@ W=/tmp/matinv_prof_$$
 mkdir -p $OUT $W
 cd /tmp && export TMPDIR=/tmp
 
-# the driver's command by itself first (under the profiler the host side of the mixed-size workload is several times slower), then traced
-python3 $R/bench.py > $OUT/${TAG}_bench_default.json 2> $W/plain.err
-rocprofv3 --kernel-trace --stats -d $W -o trace -- python3 $R/bench.py --steps 20 --warmup 3 > $OUT/${TAG}_bench_default_under_rocprofv3.json 2> $W/trace.err
-python3 $R/tools/rocprof_summary.py $W/trace_results.db "$TAG: rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3" > $OUT/${TAG}_bench_default_kernel_trace.txt
+# the full run by itself first (under the profiler the host side of the mixed-size workload is several times slower), then traced
+python3 $R/bench.py --full > $OUT/${TAG}_bench_default.json 2> $W/plain.err
+rocprofv3 --kernel-trace --stats -d $W -o trace -- python3 $R/bench.py --full --steps 20 --warmup 3 > $OUT/${TAG}_bench_default_under_rocprofv3.json 2> $W/trace.err
+python3 $R/tools/rocprof_summary.py $W/trace_results.db "$TAG: rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 3" > $OUT/${TAG}_bench_default_kernel_trace.txt
 
-# the headline workload alone: the default line above also launches the headline kernel on other batch sizes (end-to-end chunks,
+# the headline workload alone: the --full line above also launches the headline kernel on other batch sizes (end-to-end chunks,
 # residual checks), which pollutes its average; here every launch of it is one timed-size step
 rocprofv3 --kernel-trace --stats -d $W -o headline -- python3 $R/bench.py --steps 20 --warmup 5 --no-others --no-cpu-baseline > $OUT/${TAG}_bench_headline.json 2> $W/headline.err
 python3 $R/tools/rocprof_summary.py $W/headline_results.db "$TAG: rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-others --no-cpu-baseline (the headline workload alone: every launch of its kernel is one 100 000-matrix step)" > $OUT/${TAG}_bench_headline_kernel_trace.txt
