@@ -6,8 +6,8 @@ the reference's spelling is kept). Two layers:
 
 * host-pointer family ``*_batched_gpu(n, As, aInvs, batchSize)`` on numpy arrays: calls the identically named
   C symbol (H2D + kernel + D2H inside, synchronous), exactly what ``inverse_bench`` times;
-* device family on torch CUDA tensors: ``inverse_batched`` / ``mean_batched`` / ``variance_batched`` call the
-  native ``matinv_*`` entry points on torch's current stream with no copies.
+* device family on torch CUDA tensors: ``inverse_batched`` / ``mean_batched`` / ``variance_batched`` / ``solve_batched``
+  call the native ``matinv_*`` entry points on torch's current stream with no copies.
 
 A batch is flat memory: matrix k occupies ``[k*n*n, (k+1)*n*n)``, column-major (element (r, c) at c*n + r).
 torch is used for device memory and streams only; all arithmetic runs in libmatinv_hip.so.
@@ -212,6 +212,59 @@ def calcluateVariance(n, As, Bs, Cs, Es, Variances=None, batchSize=None, info=No
             ctypes.c_void_p(Cs.data_ptr()), ctypes.c_void_p(Es.data_ptr()), ctypes.c_void_p(Variances.data_ptr()),
             batchSize, ctypes.c_void_p(info.data_ptr()) if info is not None else None, _stream_ptr(Bs)))
     return Variances
+
+
+def solve_batched(A, B, n: int, nrhs: int, algo: int = ALGO_GAUSS_JORDAN, info=None, out=None, kernel: int = KERNEL_AUTO,
+                  batch: int | None = None, strideA: int | None = None, strideB: int | None = None, strideX: int | None = None):
+    """X_k = A_k^-1 B_k on device tensors, torch's current stream, no copies (matinv_solve_batched_ex; asynchronous).
+
+    A: `batch` n x n matrices, column-major, matrix k at element k*strideA (default n*n). B: n x nrhs column-major (column r
+    at r*n), matrix k at k*strideB (default n*nrhs). out: X in B's layout with strideX (default strideB); may be B itself
+    (solved in place); allocated when None. info: optional int32[batch]. ALGO_CHOLESKY reads A's lower triangle only.
+    Returns out.
+    """
+    import torch
+    _require_cuda(A, B, out, info)
+    strideA = n * n if strideA is None else int(strideA)
+    strideB = n * nrhs if strideB is None else int(strideB)
+    if batch is None:
+        batch = A.numel() // strideA
+    if out is None:
+        out = torch.empty_like(B)
+    strideX = strideB if strideX is None else int(strideX)
+    if A.dtype != B.dtype or out.dtype != B.dtype:
+        raise TypeError("A, B and out must have one dtype")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batch):
+        raise ValueError("info must be an int32 tensor with at least `batch` elements")
+    with torch.cuda.device(A.device):
+        _lib.check(_lib.lib().matinv_solve_batched_ex(
+            algo, _torch_dtype_code(A), n, nrhs, ctypes.c_void_p(A.data_ptr()), strideA, ctypes.c_void_p(B.data_ptr()), strideB,
+            ctypes.c_void_p(out.data_ptr()), strideX, batch, ctypes.c_void_p(info.data_ptr()) if info is not None else None,
+            _stream_ptr(A), kernel))
+    return out
+
+
+def solve_batched_host(As: np.ndarray, Bs: np.ndarray, n: int, nrhs: int, algo: int = ALGO_GAUSS_JORDAN):
+    """matinv_solve_batched_host on numpy batches (packed, column-major): returns (X, info). Synchronous."""
+    As = np.ascontiguousarray(As)
+    Bs = np.ascontiguousarray(Bs)
+    if As.dtype != Bs.dtype:
+        raise TypeError("As and Bs must have one dtype")
+    batch = As.size // (n * n)
+    if Bs.size < batch * n * nrhs:
+        raise ValueError("Bs smaller than batch*n*nrhs")
+    out = np.empty_like(Bs)
+    info = np.zeros(batch, dtype=np.int32)
+    _lib.check(_lib.lib().matinv_solve_batched_host(
+        algo, _np_dtype_code(As.dtype), n, nrhs, As.ctypes.data_as(ctypes.c_void_p), Bs.ctypes.data_as(ctypes.c_void_p),
+        out.ctypes.data_as(ctypes.c_void_p), batch, info.ctypes.data_as(ctypes.c_void_p)))
+    return out, info
+
+
+def solve_kernel_name(algo: int, dtype, n: int, nrhs: int, kernel: int = KERNEL_AUTO) -> str:
+    """matinv_solve_kernel_name: the first kernel a solve request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_solve_kernel_name(algo, code, n, nrhs, kernel).decode()
 
 
 mean_batched = calcluateMean

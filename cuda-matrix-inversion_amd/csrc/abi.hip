@@ -502,6 +502,115 @@ int inverse_table(int algo, int n, T *const *hostIn, T *const *hostOut, size_t b
     return rc;
 }
 
+// ---- batched linear solve X = A^-1 B (matinv_solve_batched) ------------------------------------------------------------------
+// Which path a solve request takes: the fused bordered tile kernel (or, under MATINV_GJ_PIVOT, the row solve) for 16 < n <= 64 and
+// nrhs <= 16; otherwise the composed path (inverse of `family` into a scratch block, then the batched product).
+enum { SOLVE_FUSED = 0, SOLVE_ROW = 1, SOLVE_COMPOSED = 2 };
+int solve_route(int algo, int n, int nrhs, int kernel, int &family)
+{
+    family = MATINV_KERNEL_AUTO;
+    const bool fused = solve_tile_supports(n, nrhs);
+    if (kernel == MATINV_KERNEL_TILE) {
+        if (!fused)
+            return fail(MATINV_ERR_UNSUPPORTED, "the fused solve serves 16 < n <= 64 and nrhs <= 16 only (n=%d, nrhs=%d)", n, nrhs);
+        return SOLVE_FUSED;
+    }
+    if (kernel == MATINV_KERNEL_AUTO && fused)
+        return (algo == MATINV_ALGO_GAUSS_JORDAN && gj_policy() == MATINV_GJ_PIVOT) ? SOLVE_ROW : SOLVE_FUSED;
+    family = kernel;
+    return SOLVE_COMPOSED;
+}
+
+int solve_check_args(int algo, int dtype, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB, void *dX,
+                     size_t strideX, size_t batch, int kernel)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (nrhs < 1) return fail(MATINV_ERR_ARG, "nrhs must be >= 1 (got %d)", nrhs);
+    if (algo != MATINV_ALGO_GAUSS_JORDAN && algo != MATINV_ALGO_CHOLESKY) return fail(MATINV_ERR_ARG, "unknown algorithm %d", algo);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (kernel < MATINV_KERNEL_AUTO || kernel > MATINV_KERNEL_TILEP) return fail(MATINV_ERR_ARG, "unknown kernel family %d", kernel);
+    if (batch == 0) return MATINV_OK;
+    if (!dA || !dB || !dX) return fail(MATINV_ERR_ARG, "null device pointer");
+    const size_t nb = (size_t)n * (size_t)nrhs;
+    if (batch > 1 && (strideA < (size_t)n * n || strideB < nb || strideX < nb))
+        return fail(MATINV_ERR_ARG, "stride too small (strideA >= n*n, strideB and strideX >= n*nrhs)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    return MATINV_OK;
+}
+
+template <class T>
+int solve_strided(int algo, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB, void *dX, size_t strideX,
+                  size_t batch, int *dInfo, hipStream_t stream, int kernel)
+{
+    int family = MATINV_KERNEL_AUTO;
+    const int route = solve_route(algo, n, nrhs, kernel, family);
+    if (route < 0) return route;
+    int rc = check_device();
+    if (rc) return rc;
+    BatchRef<const T> A{static_cast<const T *>(dA), strideA, nullptr};
+    BatchRef<const T> B{static_cast<const T *>(dB), strideB, nullptr};
+    BatchRef<T> X{static_cast<T *>(dX), strideX, nullptr};
+    hipError_t e = hipSuccess;
+    if (route == SOLVE_FUSED) {
+        e = launch_solve_tile<T>(algo, n, nrhs, A, B, X, batch, dInfo, stream);
+    } else if (route == SOLVE_ROW) {
+        e = launch_solve_row<T>(n, nrhs, A, B, X, batch, dInfo, stream);
+    } else {
+        // composed: k-range chunks whose inverses fit the blocked-path workspace cap, each inverted by the forced (or automatic)
+        // family into scratch -- its own info and NaN contract -- then X = Ainv B
+        const size_t mat = (size_t)n * n;
+        size_t chunk = blocked_workspace_cap() / (mat * sizeof(T));
+        if (chunk < 1) chunk = 1;
+        if (chunk > batch) chunk = batch;
+        T *inv = nullptr;
+        e = scratch_alloc(reinterpret_cast<void **>(&inv), chunk * mat * sizeof(T), stream);
+        if (e != hipSuccess) return fail_hip(e, "solve workspace");
+        for (size_t off = 0; off < batch && rc == MATINV_OK && e == hipSuccess; off += chunk) {
+            const size_t cnt = batch - off < chunk ? batch - off : chunk;
+            BatchRef<const T> Ac{A.base + off * strideA, strideA, nullptr};
+            BatchRef<T> Inv{inv, mat, nullptr};
+            rc = inverse_dispatch<T>(algo, n, Ac, Inv, cnt, dInfo ? dInfo + off : nullptr, stream, family);
+            if (rc == MATINV_OK)
+                e = launch_solve_gemm<T>(n, nrhs, inv, BatchRef<const T>{B.base + off * strideB, strideB, nullptr},
+                                         BatchRef<T>{X.base + off * strideX, strideX, nullptr}, cnt, stream);
+        }
+        const hipError_t e2 = scratch_free(inv, stream);
+        if (rc != MATINV_OK) return rc;
+        if (e == hipSuccess) e = e2;
+    }
+    if (e != hipSuccess) return fail_hip(e, "solve launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int solve_host(int algo, int n, int nrhs, const void *hA, const void *hB, void *hX, size_t batch, int *info)
+{
+    const size_t ea = (size_t)n * n * batch, eb = (size_t)n * nrhs * batch;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dA = nullptr, *dB = nullptr, *dX = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dA), ea * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dB), eb * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dX), eb * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dA, hA, ea * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dB, hB, eb * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        rc = solve_strided<T>(algo, n, nrhs, dA, (size_t)n * n, dB, (size_t)n * nrhs, dX, (size_t)n * nrhs, batch, dInfo, nullptr,
+                              MATINV_KERNEL_AUTO);
+    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hX, dX, eb * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dA);
+    staging_free(dB);
+    staging_free(dX);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "solve host<->device");
+    return MATINV_OK;
+}
+
 template <class T>
 int gp_dispatch(int n, const void *a, const void *B, const void *c, const void *d, const void *e_, void *out,
                 size_t batch, int *dInfo, void *stream, bool variance)
@@ -819,6 +928,43 @@ const char *matinv_kernel_name(int algo, int dtype, int n, int kernel)
         return f64 ? "matinv_bgp_update<double>" : "matinv_bgp_update<float>";  // the trailing update: most of the time
     default: return "";
     }
+}
+
+int matinv_solve_batched_ex(int algo, int dtype, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB, void *dX,
+                            size_t strideX, size_t batch, int *dInfo, void *stream, int kernel)
+{
+    int rc = solve_check_args(algo, dtype, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, kernel);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return solve_strided<double>(algo, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, dInfo, st, kernel);
+    return solve_strided<float>(algo, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, dInfo, st, kernel);
+}
+
+int matinv_solve_batched(int algo, int dtype, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB, void *dX,
+                         size_t strideX, size_t batch, int *dInfo, void *stream)
+{
+    return matinv_solve_batched_ex(algo, dtype, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, dInfo, stream, MATINV_KERNEL_AUTO);
+}
+
+const char *matinv_solve_kernel_name(int algo, int dtype, int n, int nrhs, int kernel)
+{
+    if (solve_check_args(algo, dtype, n, nrhs, nullptr, 0, nullptr, 0, nullptr, 0, 0, kernel) != MATINV_OK || n > 1024) return "";
+    int family = MATINV_KERNEL_AUTO;
+    const int route = solve_route(algo, n, nrhs, kernel, family);
+    const bool f64 = dtype == MATINV_F64;
+    if (route == SOLVE_FUSED) return name_solve_tile(f64, algo == MATINV_ALGO_CHOLESKY, n);
+    if (route == SOLVE_ROW) return name_solve_row(f64, n, nrhs);
+    if (route == SOLVE_COMPOSED) return matinv_kernel_name(algo, dtype, n, family);
+    return "";
+}
+
+int matinv_solve_batched_host(int algo, int dtype, int n, int nrhs, const void *hA, const void *hB, void *hX, size_t batch, int *info)
+{
+    int rc = solve_check_args(algo, dtype, n, nrhs, hA, (size_t)n * n, hB, (size_t)n * nrhs, hX, (size_t)n * nrhs, batch,
+                              MATINV_KERNEL_AUTO);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return solve_host<double>(algo, n, nrhs, hA, hB, hX, batch, info);
+    return solve_host<float>(algo, n, nrhs, hA, hB, hX, batch, info);
 }
 
 int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dDs,

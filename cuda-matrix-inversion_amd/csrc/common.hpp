@@ -285,6 +285,34 @@ hipError_t launch_gp_spd_tile<double>(int n, const double *As, const double *Bs,
 template <>
 hipError_t launch_gp_spd_tile<float>(int n, const float *As, const float *Bs, const float *Cs, const float *Ds, const float *Es,
                                      float *out, size_t batch, int *info, hipStream_t stream);
+// Batched linear solve X = A^-1 B (matinv_solve_batched). B, X: n x nrhs column-major per matrix.
+// (a) fused bordered MFMA tile kernel, 16 < n <= 64, nrhs <= 16, both algorithms (solve_tile_kernels.hip, solve_tile_f32_kernels.hip);
+//     Gauss-Jordan rejects go to (b) through a device work list in the same stream
+bool solve_tile_supports(int n, int nrhs);
+template <class T>
+hipError_t launch_solve_tile(int algo, int n, int nrhs, BatchRef<const T> A, BatchRef<const T> B, BatchRef<T> X, size_t batch, int *info,
+                             hipStream_t stream);
+template <>
+hipError_t launch_solve_tile<double>(int algo, int n, int nrhs, BatchRef<const double> A, BatchRef<const double> B, BatchRef<double> X,
+                                     size_t batch, int *info, hipStream_t stream);
+template <>
+hipError_t launch_solve_tile<float>(int algo, int n, int nrhs, BatchRef<const float> A, BatchRef<const float> B, BatchRef<float> X,
+                                    size_t batch, int *info, hipStream_t stream);
+const char *name_solve_tile(bool f64, bool spd, int n);
+// (b) pivoting row solve, n <= 64, nrhs <= 16 (solve_row_kernels.hip): whole batch, or the matrices of a work list
+bool solve_row_supports(int n, int nrhs);
+template <class T>
+hipError_t launch_solve_row(int n, int nrhs, BatchRef<const T> A, BatchRef<const T> B, BatchRef<T> X, size_t batch, int *info,
+                            hipStream_t stream);
+template <class T>
+hipError_t launch_solve_row_worklist(int n, int nrhs, BatchRef<const T> A, BatchRef<const T> B, BatchRef<T> X, const int *work_count,
+                                     const int *work_list, int *info, hipStream_t stream);
+const char *name_solve_row(bool f64, int n, int nrhs);
+// (c) product step of the composed path: X_k = Ainv_k B_k, Ainv packed (stride n^2), `count` matrices (solve_gemm_kernels.hip)
+template <class T>
+hipError_t launch_solve_gemm(int n, int nrhs, const T *Ainv, BatchRef<const T> B, BatchRef<T> X, size_t count, hipStream_t stream);
+const char *name_solve_gemm(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 const char *name_gp_lds(bool f64);

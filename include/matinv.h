@@ -114,6 +114,31 @@ int matinv_select_kernel(int algo, int dtype, int n);
 /* Name of the __global__ function a (algo, dtype, n, kernel) request launches -- the name rocprofv3 reports. */
 const char *matinv_kernel_name(int algo, int dtype, int n, int kernel);
 
+/* Batched linear solve X_k = A_k^-1 B_k without forming the inverse in memory (for 16 < n <= 64 and nrhs <= 16).
+ *   dA      in : n x n, column-major, matrix k at dA + k*strideA (strideA >= n*n). Never written. MATINV_ALGO_CHOLESKY reads
+ *                only the lower triangle (SPD input), MATINV_ALGO_GAUSS_JORDAN serves general matrices.
+ *   dB      in : n x nrhs, column-major (column r at r*n), matrix k at dB + k*strideB (strideB >= n*nrhs). Never written.
+ *   dX      out: n x nrhs like B, stride strideX. May be exactly dB with strideX == strideB (in place); partial overlap is undefined.
+ *   dInfo   out: optional int[batch] (device), the codes of matinv_inverse_batched: for a structurally singular (Gauss-Jordan) or
+ *                clearly indefinite (Cholesky) A_k the same value as the inverse reports. For info != 0, X_k is all NaN.
+ *   stream     : hipStream_t as void*. Asynchronous; no host synchronisation (except under MATINV_DEBUG_REJECTS).
+ * Paths: 16 < n <= 64 and nrhs <= 16: one fused MFMA tile kernel per batch (A^T with B^T as a border tile row); Gauss-Jordan
+ * matrices its natural pivot order rejects are solved again with partial pivoting in the same stream (under MATINV_GJ_PIVOT
+ * that row solve takes the whole batch). Elsewhere (n <= 1024): the inverse of matinv_inverse_batched_ex into a scratch block,
+ * in k-range chunks of at most the blocked-path workspace cap, then a batched product. X_k depends on matrix k alone.
+ * batch == 0 is a no-op; bad arguments return MATINV_ERR_ARG without touching a device; n > 1024: MATINV_ERR_UNSUPPORTED. */
+int matinv_solve_batched(int algo, int dtype, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB,
+                         void *dX, size_t strideX, size_t batch, int *dInfo, void *stream);
+/* Same, forcing a path: MATINV_KERNEL_AUTO = as above; MATINV_KERNEL_TILE = the fused kernel (plus its row-solve fallback) only,
+ * MATINV_ERR_UNSUPPORTED outside its range; any other family = the composed path with that family doing the inversion. */
+int matinv_solve_batched_ex(int algo, int dtype, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB,
+                            void *dX, size_t strideX, size_t batch, int *dInfo, void *stream, int kernel);
+/* Name of the first __global__ function a solve request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_solve_kernel_name(int algo, int dtype, int n, int nrhs, int kernel);
+/* Host-pointer form (packed: stride n*n for A, n*nrhs for B and X; `info` optional host int[batch]). Synchronous. */
+int matinv_solve_batched_host(int algo, int dtype, int n, int nrhs, const void *hA, const void *hB, void *hX, size_t batch,
+                              int *info);
+
 /* Fused Gaussian-process pipeline, device-resident (replaces calcluateMean / calcluateVariance,
  * src/gauss_bench.cu:127-265,275-409: addDiagonal + batched inverse + two gemmBatched):
  *   means[k] = a_k^T (B_k + diag(c_k))^-1 d_k
