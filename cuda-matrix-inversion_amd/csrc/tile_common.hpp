@@ -91,6 +91,15 @@ __device__ __forceinline__ void note_fail(unsigned long long &bad, float v)
 {
     asm volatile("v_cmp_nle_f32_e64 vcc, |%1|, 4.0\n\ts_or_b64 %0, %0, vcc" : "+s"(bad) : "v"(v) : "vcc");
 }
+// the same, lanes in `skip` exempt: one compare and a scalar mask instead of a select of the tested value per lane
+__device__ __forceinline__ void note_fail_except(unsigned long long &bad, double v, unsigned long long skip)
+{
+    asm volatile("v_cmp_nle_f64_e64 vcc, |%1|, 4.0\n\ts_andn2_b64 vcc, vcc, %2\n\ts_or_b64 %0, %0, vcc" : "+s"(bad) : "v"(v), "s"(skip) : "vcc", "scc");
+}
+__device__ __forceinline__ void note_fail_except(unsigned long long &bad, float v, unsigned long long skip)
+{
+    asm volatile("v_cmp_nle_f32_e64 vcc, |%1|, 4.0\n\ts_andn2_b64 vcc, vcc, %2\n\ts_or_b64 %0, %0, vcc" : "+s"(bad) : "v"(v), "s"(skip) : "vcc", "scc");
+}
 __device__ __forceinline__ float fast_rcp(float x)
 {
     float r = __builtin_amdgcn_rcpf(x);
@@ -223,13 +232,15 @@ struct PanelSolve {
             const int ti = s - 6;
             const T *w = &panel[(16 * ti + c) * 4];
             const T w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-            T v = -fma_t(w3, x3, fma_t(w2, x2, fma_t(w1, x1, w0 * x0)));
+            // -(w . x) with the negation on the inputs: the FMAs' neg modifiers instead of a sign flip afterwards (the same
+            // bits: round-to-nearest is symmetric)
+            T v = fma_t(-w3, x3, fma_t(-w2, x2, fma_t(-w1, x1, -w0 * x0)));
             if (ti == tK) {
                 // pivot rows: D^-1 itself (their C operand is zeroed), exempt from the multiplier test
                 const int m = G::piv(c);
                 const T x01 = (m & 1) ? x1 : x0, x23 = (m & 1) ? x3 : x2;
                 const T xm = (m & 2) ? x23 : x01;
-                if (!SPD) note_fail(bad, panel_lane ? (T)0 : v);
+                if (!SPD) note_fail_except(bad, v, __ballot(panel_lane));
                 v = panel_lane ? xm : v;
             } else {
                 if (!SPD) note_fail(bad, v);

@@ -48,54 +48,128 @@ namespace matinv {
 // 5.+6. B operand (pivot rows as they stand, I_4 on the pivot columns) and C operand (zero on the pivot columns: the
 // MFMA then leaves Aop * I_4 = the new K columns there; zero on the pivot rows: they become D^-1 * W[K,:], a pure
 // product -- no cancellation, and the step stays exactly equivariant under power-of-two scaling of the input).
-// Written as asm since r02: (i) the B operand is a copy of ONE register of each tile of tile row tK, which is then zeroed --
-// as C++ hipcc copies the whole 4-register tile to keep the old value alive (768 v_mov per 64 x 64 matrix); (ii) the pivot
-// columns are zeroed under a narrowed EXEC instead of 4 NT selects on 64-bit values (2 v_cndmask each). 272 VALU
-// instructions fewer per 64 x 64 matrix. Every block ends in s_nop 1: the two wait states a VALU write needs before an MFMA
-// reads the register as C (hipcc pads nothing inside an asm block).
+// ONE asm block per block step (r05; since r02 it was 2 NT blocks, each with its own s_nop):
+//   (i)  the B operand is a copy of ONE register of each tile of tile row tK, which is then zeroed -- as C++ hipcc copies
+//        the whole 4-register tile to keep the old value alive (768 v_mov per 64 x 64 matrix);
+//   (ii) under EXEC narrowed to the panel lanes (a compile-time lane mask: lane l = 16 q + c, panel lanes are the 16 with
+//        blk(c) == rK), the pivot columns of tile column tK are zeroed and bop[tK] takes the I_4 entry `eye` (hoisted by the
+//        caller: blk(c) == rK and piv(c) == q  <=>  panel lane and piv(c) == q), instead of 4 NT selects on 64-bit values and a
+//        per-step select for the I_4 entries.
+// Operand order: bop[tK] and tile (tK, tK) come first, so the text depends on NT only (`j` walks tK, tK + 1, ... mod NT).
+// Element rK of tile (tK, tK) is a pivot-row register: zeroed in (i) in every lane, it is not bound a second time in (ii).
+// The block ends in s_nop 1 before EXEC is restored: the two wait states a VALU write needs before an MFMA reads the register
+// as A, B or C (hipcc pads nothing inside an asm block). Every write of the block is at or before the last move, so that one
+// pad covers all of them; the MFMAs follow after the s_mov (3 states in all).
+#define MATINV_PREP_ROW(MOV, b, a) MOV " %" #b ", %" #a "\n\t" MOV " %" #a ", 0\n\t"
+#define MATINV_PREP_ZERO(MOV, a) MOV " %" #a ", 0\n\t"
+#define MATINV_PREP_TAIL(MOV, save, eye) MOV " %0, %" #eye "\n\ts_nop 1\n\ts_mov_b64 exec, %" #save
+#define MATINV_PREP_SAVE(save, mask) "s_and_saveexec_b64 %" #save ", %" #mask "\n\t"
 template <int NT, class T>
-__device__ __forceinline__ void prep_operands(typename TileGeo<T>::vec4 (&acc)[NT][NT], T (&bop)[NT], int kb, int q, int c)
+__device__ __forceinline__ void prep_operands(typename TileGeo<T>::vec4 (&acc)[NT][NT], T (&bop)[NT], int kb, T eye)
 {
-    typedef TileGeo<T> G;
+    static_assert(NT >= 1 && NT <= 4, "prep_operands: one asm text per tile count");
     const int tK = kb >> 2, rK = kb & 3;
-    const bool panel_lane = G::blk(c) == rK;
-    const bool diag_lane = panel_lane && (G::piv(c) == q);
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj) {
-        if constexpr (sizeof(T) == 8)
-            asm volatile("v_mov_b64_e32 %0, %1\n\tv_mov_b64_e32 %1, 0\n\ts_nop 1" : "=&v"(bop[tj]), "+v"(acc[tK][tj][rK]));
+    // panel lanes of block rK: f64 lanes c = 4 rK .. 4 rK + 3 of every lane group, f32 lanes c with c & 3 == rK
+    const unsigned long long pmask = sizeof(T) == 8 ? 0x000F000F000F000FULL << (4 * rK) : 0x1111111111111111ULL << rK;
+    unsigned long long save;
+    auto J = [&](int i) { return (tK + i) % NT; };
+    auto R = [&](int i) { return (rK + i) & 3; };
+#define ROW(i) acc[tK][J(i)][rK]
+#define COL(i, r) acc[J(i)][tK][R(r)]
+    if constexpr (sizeof(T) == 8) {
+#define MV "v_mov_b64_e32"
+        if constexpr (NT == 1)
+            asm volatile(MATINV_PREP_ROW(MV, 0, 1) MATINV_PREP_SAVE(5, 6)
+                         MATINV_PREP_ZERO(MV, 2) MATINV_PREP_ZERO(MV, 3) MATINV_PREP_ZERO(MV, 4) MATINV_PREP_TAIL(MV, 5, 7)
+                         : "=&v"(bop[J(0)]), "+v"(ROW(0)), "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
+        else if constexpr (NT == 2)
+            asm volatile(MATINV_PREP_ROW(MV, 0, 2) MATINV_PREP_ROW(MV, 1, 3) MATINV_PREP_SAVE(11, 12)
+                         MATINV_PREP_ZERO(MV, 4) MATINV_PREP_ZERO(MV, 5) MATINV_PREP_ZERO(MV, 6)
+                         MATINV_PREP_ZERO(MV, 7) MATINV_PREP_ZERO(MV, 8) MATINV_PREP_ZERO(MV, 9) MATINV_PREP_ZERO(MV, 10)
+                         MATINV_PREP_TAIL(MV, 11, 13)
+                         : "=&v"(bop[J(0)]), "=&v"(bop[J(1)]), "+v"(ROW(0)), "+v"(ROW(1)),
+                           "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)),
+                           "+v"(COL(1, 0)), "+v"(COL(1, 1)), "+v"(COL(1, 2)), "+v"(COL(1, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
+        else if constexpr (NT == 3)
+            asm volatile(MATINV_PREP_ROW(MV, 0, 3) MATINV_PREP_ROW(MV, 1, 4) MATINV_PREP_ROW(MV, 2, 5) MATINV_PREP_SAVE(17, 18)
+                         MATINV_PREP_ZERO(MV, 6) MATINV_PREP_ZERO(MV, 7) MATINV_PREP_ZERO(MV, 8)
+                         MATINV_PREP_ZERO(MV, 9) MATINV_PREP_ZERO(MV, 10) MATINV_PREP_ZERO(MV, 11) MATINV_PREP_ZERO(MV, 12)
+                         MATINV_PREP_ZERO(MV, 13) MATINV_PREP_ZERO(MV, 14) MATINV_PREP_ZERO(MV, 15) MATINV_PREP_ZERO(MV, 16)
+                         MATINV_PREP_TAIL(MV, 17, 19)
+                         : "=&v"(bop[J(0)]), "=&v"(bop[J(1)]), "=&v"(bop[J(2)]), "+v"(ROW(0)), "+v"(ROW(1)), "+v"(ROW(2)),
+                           "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)),
+                           "+v"(COL(1, 0)), "+v"(COL(1, 1)), "+v"(COL(1, 2)), "+v"(COL(1, 3)),
+                           "+v"(COL(2, 0)), "+v"(COL(2, 1)), "+v"(COL(2, 2)), "+v"(COL(2, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
         else
-            asm volatile("v_mov_b32_e32 %0, %1\n\tv_mov_b32_e32 %1, 0\n\ts_nop 1" : "=&v"(bop[tj]), "+v"(acc[tK][tj][rK]));
-    }
-    bop[tK] = panel_lane ? (diag_lane ? (T)1 : (T)0) : bop[tK];
-    const unsigned long long zmask = __ballot(panel_lane);
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) {
-        unsigned long long save;
-        if constexpr (sizeof(T) == 8)
-            asm volatile("s_and_saveexec_b64 %[save], %[mask]\n\t"
-                         "v_mov_b64_e32 %0, 0\n\t"
-                         "v_mov_b64_e32 %1, 0\n\t"
-                         "v_mov_b64_e32 %2, 0\n\t"
-                         "v_mov_b64_e32 %3, 0\n\t"
-                         "s_nop 1\n\t"
-                         "s_mov_b64 exec, %[save]"
-                         : "+v"(acc[ti][tK][0]), "+v"(acc[ti][tK][1]), "+v"(acc[ti][tK][2]), "+v"(acc[ti][tK][3]), [save] "=&s"(save)
-                         : [mask] "s"(zmask)
-                         : "scc");
+            asm volatile(MATINV_PREP_ROW(MV, 0, 4) MATINV_PREP_ROW(MV, 1, 5) MATINV_PREP_ROW(MV, 2, 6) MATINV_PREP_ROW(MV, 3, 7)
+                         MATINV_PREP_SAVE(23, 24)
+                         MATINV_PREP_ZERO(MV, 8) MATINV_PREP_ZERO(MV, 9) MATINV_PREP_ZERO(MV, 10)
+                         MATINV_PREP_ZERO(MV, 11) MATINV_PREP_ZERO(MV, 12) MATINV_PREP_ZERO(MV, 13) MATINV_PREP_ZERO(MV, 14)
+                         MATINV_PREP_ZERO(MV, 15) MATINV_PREP_ZERO(MV, 16) MATINV_PREP_ZERO(MV, 17) MATINV_PREP_ZERO(MV, 18)
+                         MATINV_PREP_ZERO(MV, 19) MATINV_PREP_ZERO(MV, 20) MATINV_PREP_ZERO(MV, 21) MATINV_PREP_ZERO(MV, 22)
+                         MATINV_PREP_TAIL(MV, 23, 25)
+                         : "=&v"(bop[J(0)]), "=&v"(bop[J(1)]), "=&v"(bop[J(2)]), "=&v"(bop[J(3)]),
+                           "+v"(ROW(0)), "+v"(ROW(1)), "+v"(ROW(2)), "+v"(ROW(3)),
+                           "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)),
+                           "+v"(COL(1, 0)), "+v"(COL(1, 1)), "+v"(COL(1, 2)), "+v"(COL(1, 3)),
+                           "+v"(COL(2, 0)), "+v"(COL(2, 1)), "+v"(COL(2, 2)), "+v"(COL(2, 3)),
+                           "+v"(COL(3, 0)), "+v"(COL(3, 1)), "+v"(COL(3, 2)), "+v"(COL(3, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
+#undef MV
+    } else {
+#define MV "v_mov_b32_e32"
+        if constexpr (NT == 1)
+            asm volatile(MATINV_PREP_ROW(MV, 0, 1) MATINV_PREP_SAVE(5, 6)
+                         MATINV_PREP_ZERO(MV, 2) MATINV_PREP_ZERO(MV, 3) MATINV_PREP_ZERO(MV, 4) MATINV_PREP_TAIL(MV, 5, 7)
+                         : "=&v"(bop[J(0)]), "+v"(ROW(0)), "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
+        else if constexpr (NT == 2)
+            asm volatile(MATINV_PREP_ROW(MV, 0, 2) MATINV_PREP_ROW(MV, 1, 3) MATINV_PREP_SAVE(11, 12)
+                         MATINV_PREP_ZERO(MV, 4) MATINV_PREP_ZERO(MV, 5) MATINV_PREP_ZERO(MV, 6)
+                         MATINV_PREP_ZERO(MV, 7) MATINV_PREP_ZERO(MV, 8) MATINV_PREP_ZERO(MV, 9) MATINV_PREP_ZERO(MV, 10)
+                         MATINV_PREP_TAIL(MV, 11, 13)
+                         : "=&v"(bop[J(0)]), "=&v"(bop[J(1)]), "+v"(ROW(0)), "+v"(ROW(1)),
+                           "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)),
+                           "+v"(COL(1, 0)), "+v"(COL(1, 1)), "+v"(COL(1, 2)), "+v"(COL(1, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
+        else if constexpr (NT == 3)
+            asm volatile(MATINV_PREP_ROW(MV, 0, 3) MATINV_PREP_ROW(MV, 1, 4) MATINV_PREP_ROW(MV, 2, 5) MATINV_PREP_SAVE(17, 18)
+                         MATINV_PREP_ZERO(MV, 6) MATINV_PREP_ZERO(MV, 7) MATINV_PREP_ZERO(MV, 8)
+                         MATINV_PREP_ZERO(MV, 9) MATINV_PREP_ZERO(MV, 10) MATINV_PREP_ZERO(MV, 11) MATINV_PREP_ZERO(MV, 12)
+                         MATINV_PREP_ZERO(MV, 13) MATINV_PREP_ZERO(MV, 14) MATINV_PREP_ZERO(MV, 15) MATINV_PREP_ZERO(MV, 16)
+                         MATINV_PREP_TAIL(MV, 17, 19)
+                         : "=&v"(bop[J(0)]), "=&v"(bop[J(1)]), "=&v"(bop[J(2)]), "+v"(ROW(0)), "+v"(ROW(1)), "+v"(ROW(2)),
+                           "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)),
+                           "+v"(COL(1, 0)), "+v"(COL(1, 1)), "+v"(COL(1, 2)), "+v"(COL(1, 3)),
+                           "+v"(COL(2, 0)), "+v"(COL(2, 1)), "+v"(COL(2, 2)), "+v"(COL(2, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
         else
-            asm volatile("s_and_saveexec_b64 %[save], %[mask]\n\t"
-                         "v_mov_b32_e32 %0, 0\n\t"
-                         "v_mov_b32_e32 %1, 0\n\t"
-                         "v_mov_b32_e32 %2, 0\n\t"
-                         "v_mov_b32_e32 %3, 0\n\t"
-                         "s_nop 1\n\t"
-                         "s_mov_b64 exec, %[save]"
-                         : "+v"(acc[ti][tK][0]), "+v"(acc[ti][tK][1]), "+v"(acc[ti][tK][2]), "+v"(acc[ti][tK][3]), [save] "=&s"(save)
-                         : [mask] "s"(zmask)
-                         : "scc");
+            asm volatile(MATINV_PREP_ROW(MV, 0, 4) MATINV_PREP_ROW(MV, 1, 5) MATINV_PREP_ROW(MV, 2, 6) MATINV_PREP_ROW(MV, 3, 7)
+                         MATINV_PREP_SAVE(23, 24)
+                         MATINV_PREP_ZERO(MV, 8) MATINV_PREP_ZERO(MV, 9) MATINV_PREP_ZERO(MV, 10)
+                         MATINV_PREP_ZERO(MV, 11) MATINV_PREP_ZERO(MV, 12) MATINV_PREP_ZERO(MV, 13) MATINV_PREP_ZERO(MV, 14)
+                         MATINV_PREP_ZERO(MV, 15) MATINV_PREP_ZERO(MV, 16) MATINV_PREP_ZERO(MV, 17) MATINV_PREP_ZERO(MV, 18)
+                         MATINV_PREP_ZERO(MV, 19) MATINV_PREP_ZERO(MV, 20) MATINV_PREP_ZERO(MV, 21) MATINV_PREP_ZERO(MV, 22)
+                         MATINV_PREP_TAIL(MV, 23, 25)
+                         : "=&v"(bop[J(0)]), "=&v"(bop[J(1)]), "=&v"(bop[J(2)]), "=&v"(bop[J(3)]),
+                           "+v"(ROW(0)), "+v"(ROW(1)), "+v"(ROW(2)), "+v"(ROW(3)),
+                           "+v"(COL(0, 1)), "+v"(COL(0, 2)), "+v"(COL(0, 3)),
+                           "+v"(COL(1, 0)), "+v"(COL(1, 1)), "+v"(COL(1, 2)), "+v"(COL(1, 3)),
+                           "+v"(COL(2, 0)), "+v"(COL(2, 1)), "+v"(COL(2, 2)), "+v"(COL(2, 3)),
+                           "+v"(COL(3, 0)), "+v"(COL(3, 1)), "+v"(COL(3, 2)), "+v"(COL(3, 3)), "=&s"(save)
+                         : "s"(pmask), "v"(eye) : "scc");
+#undef MV
     }
+#undef ROW
+#undef COL
 }
+#undef MATINV_PREP_ROW
+#undef MATINV_PREP_ZERO
+#undef MATINV_PREP_TAIL
+#undef MATINV_PREP_SAVE
 
 // One matrix per wavefront; see the file header. T = double or float.
 // (Tried, not kept: letting a matrix that has already failed the acceptance test skip the remaining block steps through
@@ -144,6 +218,8 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
         // (addresses keep using the un-laundered lane id so they stay in saddr + 32-bit voffset + immediate form)
         const unsigned lane_off = (unsigned)(G::trow(0, l >> 4) * n + (l & 15));
         asm volatile("" : "+v"(q), "+v"(c));
+        // I_4 entry of the B operand in the panel lanes of any block (prep_operands), once per matrix
+        const T eye = G::piv(c) == q ? (T)1 : (T)0;
         // one per-lane element offset + wave-uniform (compile-time when FULL) tile offsets keep the 16*NT*NT
         // addresses out of VGPRs
         vec4 acc[NT][NT];
@@ -195,7 +271,7 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
                 // pivot rows and columns zero elsewhere) -- skipped on a wave-uniform branch. Only the last tile column
                 // can hold such blocks. (The look-ahead of the step before it has solved that panel for nothing.)
                 if (!FULL && kb > 4 * (NT - 1) && kb - 4 * (NT - 1) >= G::real_blocks(n - 16 * (NT - 1))) continue;
-                prep_operands<NT, T>(acc, bop, kb, q, c);
+                prep_operands<NT, T>(acc, bop, kb, eye);
                 if (kb + 1 < NKB) {
                     const int tn = (kb + 1) >> 2;
                     // (a) the tile column holding the next pivot columns first ...
@@ -263,7 +339,7 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
                 wave_lds_sync();
                 panel_solve<NT>(panel, kb, q, c, aop, bad);
                 wave_lds_sync();  // panel is rewritten by the next block step
-                prep_operands<NT, T>(acc, bop, kb, q, c);
+                prep_operands<NT, T>(acc, bop, kb, eye);
                 // 7. rank-4 update of every tile on the matrix cores
 #pragma unroll
                 for (int ti = 0; ti < NT; ++ti)
