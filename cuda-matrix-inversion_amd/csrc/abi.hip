@@ -864,7 +864,7 @@ int matinv_memcpy_2d(void *dst, size_t dpitch, const void *src, size_t spitch, s
     return MATINV_OK;
 }
 
-// how the adaptive Gauss-Jordan dispatch of the tile family went (tile_kernels.inc "natural order or pivot search?")
+// how the adaptive Gauss-Jordan dispatch of the tile family went (tile_kernels.hip "natural order or pivot search?")
 int matinv_tile_stats(unsigned long long *natural_launches, unsigned long long *pivot_launches, unsigned long long *last_rejected,
                       unsigned long long *last_batch)
 {

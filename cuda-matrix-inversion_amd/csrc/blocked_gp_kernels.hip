@@ -236,7 +236,7 @@ __global__ __launch_bounds__(BGP_THREADS) void matinv_bgp_finish(const T *W, con
 //     S[I,J] <- A[I,J] - sum_{k<J} S[I,k] G_k S[J,k]^T,   G_k = S[k,k]^-1,   answer = sum_k S[a,k] G_k S[d,k]^T
 // (S[I,k] G_k S[J,k]^T = L[I,k] L[J,k]^T of the Cholesky form, so the Schur complements S are the same matrices). Per panel:
 //   matinv_bldl_panel   one workgroup per 64 rows below the diagonal block (border rows included). Wave 0 inverts the 64 x 64 block
-//                       with the symmetric MFMA sweep of the one-wavefront kernels (tile_kernels.inc: 16 block steps on 10 lower
+//                       with the symmetric MFMA sweep of the one-wavefront kernels (tile_impl.hpp: 16 block steps on 10 lower
 //                       tiles held in registers; non-positive pivot = not positive definite, reported with its column), every
 //                       wave then forms its 32 x 32 part of P = S[rows, k] G_k on the matrix cores, the S operand fetched from
 //                       global memory into MFMA operand registers BEFORE the sweep starts. P replaces the panel in place; the raw

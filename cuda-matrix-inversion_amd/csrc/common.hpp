@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/matinv.h"
 
 namespace matinv {
@@ -21,6 +23,49 @@ hipError_t scratch_free(void *p, hipStream_t stream);
 void scratch_retire_stream(hipStream_t stream);  // after synchronising a stream that is about to be destroyed
 void blocked_gp_release_graphs();                // the cached launch-chain graphs of blocked_gp_kernels.hip (they hold scratch pointers)
 void scratch_release_device();                   // after hipDeviceSynchronize: hipFree everything not in use
+
+// The work-list block of a launcher: `count` ints of scratch, the first `zeroed` of them cleared, body(ws) enqueued behind that
+// and the block freed in stream order. Returns the first error; body runs only when the allocation and the clearing succeeded.
+template <class Body>
+hipError_t with_scratch_ints(size_t count, size_t zeroed, hipStream_t stream, Body &&body)
+{
+    int *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), count * sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(ws, 0, zeroed * sizeof(int), stream);
+    if (e == hipSuccess) e = body(ws);
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+// Compile-time tile count of a launch: f(std::integral_constant<int, NT>{}) for the run-time nt in [LO, HI]; any other nt takes HI
+// (the `default:` of the switch this replaces).
+template <int LO, int HI, class F>
+decltype(auto) with_nt(int nt, F &&f)
+{
+    if constexpr (LO == HI) {
+        return f(std::integral_constant<int, HI>{});
+    } else {
+        if (nt == LO) return f(std::integral_constant<int, LO>{});
+        return with_nt<LO + 1, HI>(nt, f);
+    }
+}
+// What a tile kernel is instantiated on: NT tiles of 16 per dimension, and FULL = n == 16 * NT (no partial tile: constant offsets,
+// no bounds checks). The launchers and the kernel_name strings both derive it from these functions.
+struct TileShape {
+    int nt;
+    bool full;
+};
+constexpr TileShape tile_shape(int n) { return {(n + 15) / 16, n % 16 == 0}; }
+// f(NT, std::bool_constant<FULL>{}) as with_nt; FULL only for the nt the shape names
+template <int LO, int HI, class F>
+decltype(auto) with_tile(TileShape s, F &&f)
+{
+    return with_nt<LO, HI>(s.nt, [&](auto nt) -> decltype(auto) {
+        if (s.full && s.nt == nt) return f(nt, std::true_type{});
+        return f(nt, std::false_type{});
+    });
+}
 
 // Where matrix k of a batch lives: either base + k*stride, or table[k] (the reference's
 // "array of device pointers" form, /root/reference/src/helper.cu:103-118).
@@ -125,6 +170,12 @@ hipError_t launch_chol_blocked(int n, BatchRef<const T> A, BatchRef<T> X, size_t
 // rounds of resident workgroups in the grids of the MFMA-tile kernels (each workgroup strides over the batch);
 // MATINV_TILE_GRID_MULT overrides the default for A/B measurements (tile_kernels.hip)
 unsigned tile_grid_rounds();
+// grid of a tile-kernel launch: one workgroup per matrix, at most `rounds` rounds of per_cu resident workgroups on each of 256 CUs
+inline unsigned tile_grid(size_t batch, unsigned per_cu, unsigned rounds = tile_grid_rounds())
+{
+    const unsigned cap = 256u * per_cu * rounds;
+    return (unsigned)(batch < cap ? batch : cap);
+}
 
 // blocked Gauss-Jordan with partial pivoting for large general matrices (blocked_gj_kernels.hip)
 bool blocked_gj_supports(int n);
@@ -180,42 +231,18 @@ const char *name_spd_tile(bool f64, int n);
 bool tilep_supports(int n);
 template <class T>
 hipError_t launch_gj_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream);
-template <>
-hipError_t launch_gj_tilep<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, int *info, hipStream_t stream);
-template <>
-hipError_t launch_gj_tilep<float>(int n, BatchRef<const float> A, BatchRef<float> X, size_t batch, int *info, hipStream_t stream);
 // work-list form: inverts in_list[0 .. *in_count) (device memory); singular ones go on to the ROW kernel through
 // (bad_count, bad_list), zeroed by the caller; hint_out (pinned host memory, may be null) receives the list length
 template <class T>
 hipError_t launch_gj_tilep_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count, const int *in_list,
                                     int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many = false);
-template <>
-hipError_t launch_gj_tilep_worklist<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, const int *in_count,
-                                            const int *in_list, int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out,
-                                            bool expect_many);
-template <>
-hipError_t launch_gj_tilep_worklist<float>(int n, BatchRef<const float> A, BatchRef<float> X, size_t batch, const int *in_count,
-                                           const int *in_list, int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out,
-                                           bool expect_many);
 const char *name_gj_tilep(bool f64, int n);
 // four wavefronts per matrix, 64 < n <= 128 (tilep4_kernels.hip)
 template <class T>
 hipError_t launch_gj_tilep4(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream);
-template <>
-hipError_t launch_gj_tilep4<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, int *info, hipStream_t stream);
-template <>
-hipError_t launch_gj_tilep4<float>(int n, BatchRef<const float> A, BatchRef<float> X, size_t batch, int *info, hipStream_t stream);
 template <class T>
 hipError_t launch_gj_tilep4_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count, const int *in_list,
                                      int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many = false);
-template <>
-hipError_t launch_gj_tilep4_worklist<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, const int *in_count,
-                                             const int *in_list, int *bad_count, int *bad_list, int *info, hipStream_t stream,
-                                             hint_t *hint_out, bool expect_many);
-template <>
-hipError_t launch_gj_tilep4_worklist<float>(int n, BatchRef<const float> A, BatchRef<float> X, size_t batch, const int *in_count,
-                                            const int *in_list, int *bad_count, int *bad_list, int *info, hipStream_t stream,
-                                            hint_t *hint_out, bool expect_many);
 const char *name_gj_tilep4(bool f64, int n);
 // r04: fixed pivot rows, searched pivot columns -- no run-time register index (tileq_kernels.hip): one wavefront per tile column,
 // general 128 < n <= 192 (f64) / 256 (f32). in_count / in_list: work-list form (nullptr: the whole batch); bad_count / bad_list: unused
@@ -223,12 +250,6 @@ const char *name_gj_tilep4(bool f64, int n);
 template <class T>
 hipError_t launch_gj_tileq(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream, const int *in_count,
                            const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list);
-template <>
-hipError_t launch_gj_tileq<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, int *info, hipStream_t stream,
-                                   const int *in_count, const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list);
-template <>
-hipError_t launch_gj_tileq<float>(int n, BatchRef<const float> A, BatchRef<float> X, size_t batch, int *info, hipStream_t stream,
-                                  const int *in_count, const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list);
 const char *name_gj_tileq(bool f64, int n);
 // general 128 < n <= 192 (f64) / 256 (f32): TILEQ (tileq_kernels.hip)
 bool tileq_supports(bool f64, int n);
@@ -254,7 +275,7 @@ hipError_t launch_gp_tile(int n, const T *As, const T *Bs, const T *Cs, const T 
                           int *info, hipStream_t stream);
 const char *name_gp_tile(bool f64, int n);
 // fused GP scalars on the SPD sweep of the Cholesky entry point (inverse in registers, folded, never stored): the sizes the
-// bordered form above no longer holds in one wavefront -- f64 80 < n <= 96, f32 96 < n <= 112 (tile_kernels.inc)
+// bordered form above no longer holds in one wavefront -- f64 80 < n <= 96, f32 96 < n <= 112 (tile_impl.hpp)
 // test hook (scratch.hip): MATINV_DEBUG_REJECTS=1 -> launchers with a work list add its final count to a running total
 hipError_t debug_note_rejects(const int *work_count, hipStream_t stream);
 long long debug_rejects(bool reset);
@@ -279,12 +300,6 @@ const char *name_spd_tile2(bool gp, int n);
 template <class T>
 hipError_t launch_gp_spd_tile(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
                               int *info, hipStream_t stream);
-template <>
-hipError_t launch_gp_spd_tile<double>(int n, const double *As, const double *Bs, const double *Cs, const double *Ds, const double *Es,
-                                      double *out, size_t batch, int *info, hipStream_t stream);
-template <>
-hipError_t launch_gp_spd_tile<float>(int n, const float *As, const float *Bs, const float *Cs, const float *Ds, const float *Es,
-                                     float *out, size_t batch, int *info, hipStream_t stream);
 // Batched linear solve X = A^-1 B (matinv_solve_batched). B, X: n x nrhs column-major per matrix.
 // (a) fused bordered MFMA tile kernel, 16 < n <= 64, nrhs <= 16, both algorithms (solve_tile_kernels.hip, solve_tile_f32_kernels.hip);
 //     Gauss-Jordan rejects go to (b) through a device work list in the same stream
@@ -292,12 +307,6 @@ bool solve_tile_supports(int n, int nrhs);
 template <class T>
 hipError_t launch_solve_tile(int algo, int n, int nrhs, BatchRef<const T> A, BatchRef<const T> B, BatchRef<T> X, size_t batch, int *info,
                              hipStream_t stream);
-template <>
-hipError_t launch_solve_tile<double>(int algo, int n, int nrhs, BatchRef<const double> A, BatchRef<const double> B, BatchRef<double> X,
-                                     size_t batch, int *info, hipStream_t stream);
-template <>
-hipError_t launch_solve_tile<float>(int algo, int n, int nrhs, BatchRef<const float> A, BatchRef<const float> B, BatchRef<float> X,
-                                    size_t batch, int *info, hipStream_t stream);
 const char *name_solve_tile(bool f64, bool spd, int n);
 // (b) pivoting row solve, n <= 64, nrhs <= 16 (solve_row_kernels.hip): whole batch, or the matrices of a work list
 bool solve_row_supports(int n, int nrhs);

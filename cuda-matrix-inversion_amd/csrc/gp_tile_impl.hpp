@@ -181,49 +181,17 @@ hipError_t launch_gp_tile(int n, const T *As, const T *Bs, const T *Cs, const T 
 {
     if (!gp_tile_supports(sizeof(T) == 8, n)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
+    return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
+        const unsigned grid = tile_grid(batch, 8u), b = (unsigned)batch;
+        with_tile<1, 6>(tile_shape(n), [&](auto NT, auto FULL) {
+            if constexpr (sizeof(T) == 8)
+                hipLaunchKernelGGL((matinv_gp_tile_f64<NT, FULL>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
+            else
+                hipLaunchKernelGGL((matinv_gp_tile_f32<NT, FULL>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
+        });
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = launch_gp_lds_worklist<T>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
         return e;
-    }
-    const int nt = (n + 15) / 16;
-    const unsigned grid = (unsigned)(batch < 256u * 8u * tile_grid_rounds() ? batch : 256u * 8u * tile_grid_rounds());
-    const unsigned b = (unsigned)batch;
-#define GP_LAUNCH(NT_)                                                                                                \
-    if constexpr (sizeof(T) == 8) {                                                                                   \
-        if (n == 16 * NT_)                                                                                            \
-            hipLaunchKernelGGL((matinv_gp_tile_f64<NT_, true>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((matinv_gp_tile_f64<NT_, false>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); \
-    } else {                                                                                                          \
-        if (n == 16 * NT_)                                                                                            \
-            hipLaunchKernelGGL((matinv_gp_tile_f32<NT_, true>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((matinv_gp_tile_f32<NT_, false>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); \
-    }
-#define GP_LAUNCH32(NT_)                                                                                              \
-    if constexpr (sizeof(T) == 4) {                                                                                   \
-        if (n == 16 * NT_)                                                                                            \
-            hipLaunchKernelGGL((matinv_gp_tile_f32<NT_, true>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((matinv_gp_tile_f32<NT_, false>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); \
-    }
-    switch (nt) {
-    case 1: GP_LAUNCH(1) break;
-    case 2: GP_LAUNCH(2) break;
-    case 3: GP_LAUNCH(3) break;
-    case 4: GP_LAUNCH(4) break;
-    case 5: GP_LAUNCH(5) break;
-    default: GP_LAUNCH(6) break;
-    }
-#undef GP_LAUNCH
-#undef GP_LAUNCH32
-    e = hipGetLastError();
-    if (e == hipSuccess) e = launch_gp_lds_worklist<T>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
+    });
 }
 }  // namespace matinv

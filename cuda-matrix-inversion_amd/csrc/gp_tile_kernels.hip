@@ -12,8 +12,9 @@ template hipError_t launch_gp_tile<double>(int, const double *, const double *, 
 
 const char *name_gp_tile(bool f64, int n)
 {
+    const TileShape s = tile_shape(n);
     static thread_local char buf[48];
-    snprintf(buf, sizeof buf, "matinv_gp_tile_%s<%d, %s>", f64 ? "f64" : "f32", (n + 15) / 16, (n % 16) == 0 ? "true" : "false");
+    snprintf(buf, sizeof buf, "matinv_gp_tile_%s<%d, %s>", f64 ? "f64" : "f32", s.nt, s.full ? "true" : "false");
     return buf;
 }
 

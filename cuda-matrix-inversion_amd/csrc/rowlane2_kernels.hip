@@ -357,14 +357,11 @@ hipError_t launch_gp_rowlane2(int n, const T *As, const T *Bs, const T *Cs, cons
 {
     if (!rowlane2_supports(n)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e == hipSuccess) e = enqueue_gp_rowlane2<T>(n, As, Bs, Cs, Ds, Es, out, batch, info, stream, ws, ws + 1);
-    if (e == hipSuccess) e = launch_gp_lds_worklist<T>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
+    return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
+        hipError_t e = enqueue_gp_rowlane2<T>(n, As, Bs, Cs, Ds, Es, out, batch, info, stream, ws, ws + 1);
+        if (e == hipSuccess) e = launch_gp_lds_worklist<T>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
+        return e;
+    });
 }
 template hipError_t launch_gp_rowlane2<double>(int, const double *, const double *, const double *, const double *, const double *, double *,
                                                size_t, int *, hipStream_t);

@@ -90,22 +90,11 @@ bool solve_tile_supports(int n, int nrhs) { return n > 16 && n <= 64 && nrhs >= 
 
 const char *name_solve_tile(bool f64, bool spd, int n)
 {
-    // [f64][spd][NT - 2][full]
-    static const char *const names[2][2][3][2] = {
-        {{{"matinv_solve_tile_f32<2, false, false>", "matinv_solve_tile_f32<2, true, false>"},
-          {"matinv_solve_tile_f32<3, false, false>", "matinv_solve_tile_f32<3, true, false>"},
-          {"matinv_solve_tile_f32<4, false, false>", "matinv_solve_tile_f32<4, true, false>"}},
-         {{"matinv_solve_tile_f32<2, false, true>", "matinv_solve_tile_f32<2, true, true>"},
-          {"matinv_solve_tile_f32<3, false, true>", "matinv_solve_tile_f32<3, true, true>"},
-          {"matinv_solve_tile_f32<4, false, true>", "matinv_solve_tile_f32<4, true, true>"}}},
-        {{{"matinv_solve_tile_f64<2, false, false>", "matinv_solve_tile_f64<2, true, false>"},
-          {"matinv_solve_tile_f64<3, false, false>", "matinv_solve_tile_f64<3, true, false>"},
-          {"matinv_solve_tile_f64<4, false, false>", "matinv_solve_tile_f64<4, true, false>"}},
-         {{"matinv_solve_tile_f64<2, false, true>", "matinv_solve_tile_f64<2, true, true>"},
-          {"matinv_solve_tile_f64<3, false, true>", "matinv_solve_tile_f64<3, true, true>"},
-          {"matinv_solve_tile_f64<4, false, true>", "matinv_solve_tile_f64<4, true, true>"}}}};
     if (n <= 16 || n > 64) return "";
-    return names[f64 ? 1 : 0][spd ? 1 : 0][(n + 15) / 16 - 2][n % 16 == 0 ? 1 : 0];
+    const TileShape s = tile_shape(n);
+    static thread_local char buf[48];
+    snprintf(buf, sizeof buf, "matinv_solve_tile_%s<%d, %s, %s>", f64 ? "f64" : "f32", s.nt, s.full ? "true" : "false", spd ? "true" : "false");
+    return buf;
 }
 
 template <class T>

@@ -1,7 +1,7 @@
 // solve_tile_impl.hpp -- fused batched linear solve X = A^-1 B on the one-wavefront MFMA tile layout, 16 < n <= 64,
 // 1 <= nrhs <= 16 (solve_tile_kernels.hip: fp64, solve_tile_f32_kernels.hip: fp32). The inverse is never formed.
 //
-// It is the natural-order Gauss-Jordan kernel of tile_kernels.inc (gj_tile_body) with one extra BORDER tile row: W = A^T
+// It is the natural-order Gauss-Jordan kernel of tile_impl.hpp (gj_tile_body) with one extra BORDER tile row: W = A^T
 // sits in the NT x NT accumulator tiles exactly as there, and Z = B^T rides below it (row r of Z = column r of B, contiguous
 // in memory, loaded like a row of W; rows nrhs .. 15 are zero). Every block step is the same blocked in-place step
 //     Aop[i,:] = -W[i,K] D^-1,   W[i,J] += Aop[i,:] W[K,J],   W[:,K] <- Aop        (one 16x16x4 MFMA per tile)
@@ -44,7 +44,7 @@ __device__ __forceinline__ void solve_panel_to_lds(T *panel, const typename Tile
 }
 
 // 5.+6. B operand (pivot rows as they stand, I_4 on the pivot columns) and C operand (zero on the pivot columns) of the live tile
-// rows and the border -- prep_operands of tile_kernels.inc restricted to those rows; asm for the reasons given there.
+// rows and the border -- prep_operands of tile_impl.hpp restricted to those rows; asm for the reasons given there.
 template <int NT, class T>
 __device__ __forceinline__ void solve_prep_operands(typename TileGeo<T>::vec4 (&acc)[NT][NT], typename TileGeo<T>::vec4 (&zacc)[NT],
                                                     T (&bop)[NT], int kb, int q, int c)
@@ -237,37 +237,58 @@ __device__ __forceinline__ void solve_tile_body(BatchRef<const T> Ain, BatchRef<
     }
 }
 
-// GJ: the fused kernel, then the row solve over the matrices it rejected (same stream, device-side work list; the list length feeds
-// the MATINV_DEBUG_REJECTS counter). Cholesky: the fused kernel alone. KERNEL(NT, FULL, SPD) launches one instantiation.
-template <class T, class Launch>
-hipError_t launch_solve_tile_impl(int algo, int n, int nrhs, BatchRef<const T> A, BatchRef<const T> B, BatchRef<T> X, size_t batch,
-                                  int *info, hipStream_t stream, Launch launch)
+template <int NT, bool FULL, bool SPD>
+__global__ __launch_bounds__(64, 2) void matinv_solve_tile_f64(BatchRef<const double> A, BatchRef<const double> B, BatchRef<double> X,
+                                                               int *info, int n, int nrhs, unsigned batch, int *work_count,
+                                                               int *work_list)
 {
-    constexpr bool F64 = sizeof(T) == 8;
+    __shared__ __attribute__((aligned(16))) double panel[16 * (NT + 1) * 4];  // [row][4 pivot columns], border rows last
+    solve_tile_body<double, NT, FULL, SPD>(A, B, X, info, n, nrhs, batch, work_count, work_list, panel);
+}
+
+// fp32: three waves per SIMD -- with four (128 registers) the 4 x 4-tile instantiation spills the border
+template <int NT, bool FULL, bool SPD>
+__global__ __launch_bounds__(64, 3) void matinv_solve_tile_f32(BatchRef<const float> A, BatchRef<const float> B, BatchRef<float> X,
+                                                               int *info, int n, int nrhs, unsigned batch, int *work_count,
+                                                               int *work_list)
+{
+    __shared__ __attribute__((aligned(16))) float panel[16 * (NT + 1) * 4];  // [row][4 pivot columns], border rows last
+    solve_tile_body<float, NT, FULL, SPD>(A, B, X, info, n, nrhs, batch, work_count, work_list, panel);
+}
+
+// GJ: the fused kernel, then the row solve over the matrices it rejected (same stream, device-side work list; the list length feeds
+// the MATINV_DEBUG_REJECTS counter). Cholesky: the fused kernel alone.
+template <class T>
+hipError_t launch_solve_tile(int algo, int n, int nrhs, BatchRef<const T> A, BatchRef<const T> B, BatchRef<T> X, size_t batch, int *info,
+                             hipStream_t stream)
+{
     if (!solve_tile_supports(n, nrhs)) return hipErrorInvalidValue;
     const bool spd = algo == MATINV_ALGO_CHOLESKY;
-    int *ws = nullptr;
-    hipError_t e = hipSuccess;
-    if (!spd) {
-        e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 4) * sizeof(int), stream);
-        if (e != hipSuccess) return e;
-        e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    }
-    // grid-stride over the batch, as the natural-order inverse (launch_gj_tile_natural)
-    const unsigned per_cu = F64 ? 8u : 16u;
-    const unsigned cap = 256u * per_cu * tile_grid_rounds();
-    const unsigned grid = (unsigned)(batch < cap ? batch : cap);
-    if (e == hipSuccess) {
-        launch((n + 15) / 16, n % 16 == 0, spd, grid, A, B, X, info, n, nrhs, (unsigned)batch, ws, ws ? ws + 4 : nullptr);
-        e = hipGetLastError();
-    }
-    if (!spd) {
+    auto launch = [&](int *work_count, int *work_list) {
+        // grid-stride over the batch, as the natural-order inverse (launch_gj_tile_natural)
+        const unsigned grid = tile_grid(batch, sizeof(T) == 8 ? 8u : 16u), b = (unsigned)batch;
+        with_tile<2, 4>(tile_shape(n), [&](auto NT, auto FULL) {
+            auto go = [&](auto SPD) {
+                if constexpr (sizeof(T) == 8)
+                    hipLaunchKernelGGL((matinv_solve_tile_f64<NT, FULL, SPD>), dim3(grid), dim3(64), 0, stream, A, B, X, info, n, nrhs, b,
+                                       work_count, work_list);
+                else
+                    hipLaunchKernelGGL((matinv_solve_tile_f32<NT, FULL, SPD>), dim3(grid), dim3(64), 0, stream, A, B, X, info, n, nrhs, b,
+                                       work_count, work_list);
+            };
+            if (spd) go(std::true_type{});
+            else go(std::false_type{});
+        });
+        return hipGetLastError();
+    };
+    if (spd) return launch(nullptr, nullptr);
+    // [0] count, [4 ..) list
+    return with_scratch_ints(batch + 4, 1, stream, [&](int *ws) {
+        hipError_t e = launch(ws, ws + 4);
         if (e == hipSuccess) e = launch_solve_row_worklist<T>(n, nrhs, A, B, X, ws, ws + 4, info, stream);
         if (e == hipSuccess) e = debug_note_rejects(ws, stream);
-        const hipError_t e2 = scratch_free(ws, stream);
-        if (e == hipSuccess) e = e2;
-    }
-    return e;
+        return e;
+    });
 }
 
 }  // namespace matinv

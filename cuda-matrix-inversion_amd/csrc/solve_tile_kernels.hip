@@ -3,38 +3,7 @@
 
 namespace matinv {
 
-template <int NT, bool FULL, bool SPD>
-__global__ __launch_bounds__(64, 2) void matinv_solve_tile_f64(BatchRef<const double> A, BatchRef<const double> B, BatchRef<double> X,
-                                                               int *info, int n, int nrhs, unsigned batch, int *work_count,
-                                                               int *work_list)
-{
-    __shared__ __attribute__((aligned(16))) double panel[16 * (NT + 1) * 4];  // [row][4 pivot columns], border rows last
-    solve_tile_body<double, NT, FULL, SPD>(A, B, X, info, n, nrhs, batch, work_count, work_list, panel);
-}
-
-template <>
-hipError_t launch_solve_tile<double>(int algo, int n, int nrhs, BatchRef<const double> A, BatchRef<const double> B, BatchRef<double> X,
-                                     size_t batch, int *info, hipStream_t stream)
-{
-    auto launch = [&](int nt, bool full, bool spd, unsigned grid, auto... args) {
-#define SOLVE_LAUNCH(NT_, FULL_, SPD_) \
-    hipLaunchKernelGGL((matinv_solve_tile_f64<NT_, FULL_, SPD_>), dim3(grid), dim3(64), 0, stream, args...)
-#define SOLVE_LAUNCH_NT(NT_)                                                  \
-    do {                                                                      \
-        if (full && spd) SOLVE_LAUNCH(NT_, true, true);                       \
-        else if (full) SOLVE_LAUNCH(NT_, true, false);                        \
-        else if (spd) SOLVE_LAUNCH(NT_, false, true);                         \
-        else SOLVE_LAUNCH(NT_, false, false);                                 \
-    } while (0)
-        switch (nt) {
-        case 2: SOLVE_LAUNCH_NT(2); break;
-        case 3: SOLVE_LAUNCH_NT(3); break;
-        default: SOLVE_LAUNCH_NT(4); break;
-        }
-#undef SOLVE_LAUNCH_NT
-#undef SOLVE_LAUNCH
-    };
-    return launch_solve_tile_impl<double>(algo, n, nrhs, A, B, X, batch, info, stream, launch);
-}
+template hipError_t launch_solve_tile<double>(int, int, int, BatchRef<const double>, BatchRef<const double>, BatchRef<double>, size_t, int *,
+                                              hipStream_t);
 
 }  // namespace matinv

@@ -1,5 +1,5 @@
 // spd_tile2_impl.hpp (instantiated by spd_tile2_kernels.hip and spd_tile2_wide*_kernels.hip, fp64) -- the symmetric blocked sweep of
-// matinv_spd_tile_f64 (tile_kernels.inc: read its header first) on TWO wavefronts per matrix, LOWER tiles only: 112 < n <= 128
+// matinv_spd_tile_f64 (tile_impl.hpp: read its header first) on TWO wavefronts per matrix, LOWER tiles only: 112 < n <= 128
 // (8 x 8 tiles, r03) and -- r04 -- 128 < n <= 176 (9 ... 11 tiles per dimension: 23 ... 33 lower tiles = up to 288 accumulator registers
 // per wave, so these run ONE wave per SIMD on VGPRs + AGPRs, two matrices per CU; before, these sizes swept ALL n^2 tiles with one
 // wavefront per tile column and one matrix per CU: 130^2 Cholesky 3.4e6 inv/s, a 2.9 x cliff behind 128^2).
@@ -17,7 +17,7 @@
 // redundantly (PanelSolve, SPD mode: A operand and the symmetric B operand), prepare their operands and issue their MFMAs.
 // (Measured and not kept: ONE wave -- taking turns -- solving the panel and publishing the A operand and the symmetric B operand
 // through LDS, two barriers per step: Cholesky 128^2 9.8e6 -> 1.07e7 inv/s, pipeline 1.17e7 -> 1.04e7 items/s: a wash.)
-// GP = the fused mean / variance on the same sweep (see SpdGp in tile_kernels.inc): diag c added while loading, a^T M^-1 d folded
+// GP = the fused mean / variance on the same sweep (see SpdGp in tile_impl.hpp): diag c added while loading, a^T M^-1 d folded
 // out of the accumulators of both waves, nothing stored.
 //
 // Replaces, for SPD input of these sizes, the Cholesky families of /root/reference/src/inverse_cholesky_gpu.cu:55-765 and

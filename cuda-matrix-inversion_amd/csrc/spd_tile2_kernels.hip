@@ -17,9 +17,7 @@ static hipError_t launch_tile2(int n, BatchRef<const double> A, BatchRef<double>
     const int nt = (n + 15) / 16;
     // n <= 128: four workgroups of two waves per CU; beyond: one wave per SIMD (VGPRs + AGPRs), two workgroups per CU (12 x 12 tiles,
     // three waves: one)
-    const unsigned resident = nt <= 8 ? 256u * 4u : (nt <= 11 ? 256u * 2u : 256u);
-    const unsigned cap = resident * tile_grid_rounds();
-    const unsigned grid = (unsigned)(batch < cap ? batch : cap);
+    const unsigned grid = tile_grid(batch, nt <= 8 ? 4u : (nt <= 11 ? 2u : 1u));
     switch (nt) {
     case 8: hipLaunchKernelGGL((matinv_spd_tile2_f64<GP>), dim3(grid), dim3(128), 0, stream, A, X, info, n, (unsigned)batch, ws, ws + 1, gp); break;
     case 9: return enqueue_spd_tile2w<9>(GP, n, A, X, grid, (unsigned)batch, info, ws, gp, stream);
@@ -35,15 +33,12 @@ hipError_t launch_spd_tile2(int n, BatchRef<const double> A, BatchRef<double> X,
 {
     if (n <= 112 || n > 192) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e == hipSuccess) e = launch_tile2<false>(n, A, X, batch, info, stream, ws, Spd2Gp<double>());
-    // n <= 128: items that are not positive definite go to the LDS Cholesky (it reports the column); beyond, the kernel finishes them
-    if (e == hipSuccess && n <= 128) e = launch_chol_lds_worklist<double>(n, A, X, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
+    return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
+        hipError_t e = launch_tile2<false>(n, A, X, batch, info, stream, ws, Spd2Gp<double>());
+        // n <= 128: items that are not positive definite go to the LDS Cholesky (it reports the column); beyond, the kernel finishes them
+        if (e == hipSuccess && n <= 128) e = launch_chol_lds_worklist<double>(n, A, X, ws, ws + 1, info, stream);
+        return e;
+    });
 }
 
 hipError_t launch_gp_spd_tile2(int n, const double *As, const double *Bs, const double *Cs, const double *Ds, const double *Es, double *out,
@@ -51,16 +46,13 @@ hipError_t launch_gp_spd_tile2(int n, const double *As, const double *Bs, const 
 {
     if (n <= 112 || n > 192) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
     BatchRef<const double> A{Bs, (size_t)n * n, nullptr};
     BatchRef<double> X{nullptr, 0, nullptr};
-    if (e == hipSuccess) e = launch_tile2<true>(n, A, X, batch, info, stream, ws, Spd2Gp<double>{As, Cs, Ds, Es, out});
-    if (e == hipSuccess && n <= 128) e = launch_gp_lds_worklist<double>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
+    return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
+        hipError_t e = launch_tile2<true>(n, A, X, batch, info, stream, ws, Spd2Gp<double>{As, Cs, Ds, Es, out});
+        if (e == hipSuccess && n <= 128) e = launch_gp_lds_worklist<double>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
+        return e;
+    });
 }
 
 const char *name_spd_tile2(bool gp, int n)

@@ -1,5 +1,8 @@
 // spd_tile2w9_kernels.hip -- the two-wavefront lower-triangle SPD sweep of 9 x 9 fp64 tiles (128 < n <= 144): Cholesky entry point and fused mean /
 // variance (spd_tile2_impl.hpp); compiled with VGPR-form MFMAs, the AGPRs as parking space (Makefile).
+#ifndef MATINV_MFMA_VGPR_FORM
+#error "build with -mllvm -amdgpu-mfma-vgpr-form=1 -DMATINV_MFMA_VGPR_FORM=1 (Makefile)"
+#endif
 #include "spd_tile2_impl.hpp"
 
 namespace matinv {

@@ -1,5 +1,8 @@
 // spd_tile3w_kernels.hip -- the lower-triangle SPD sweep of 12 x 12 fp64 tiles on THREE wavefronts: Cholesky entry point and fused mean /
 // variance (spd_tile2_impl.hpp, W = 3); compiled with VGPR-form MFMAs (Makefile).
+#ifndef MATINV_MFMA_VGPR_FORM
+#error "build with -mllvm -amdgpu-mfma-vgpr-form=1 -DMATINV_MFMA_VGPR_FORM=1 (Makefile)"
+#endif
 #include "spd_tile2_impl.hpp"
 
 namespace matinv {

@@ -292,105 +292,62 @@ static hipError_t launch_tile4(int n, BatchRef<const T> A, BatchRef<T> X, size_t
     if (SPD && (n + 15) / 16 < (sizeof(T) == 8 ? 12 : 11)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
     // Gauss-Jordan: general batches go straight to the PIVOTING kernel of this size once a natural-order launch of this size
-    // has seen most of its matrices rejected (tile_kernels.inc "natural order or pivot search?")
+    // has seen most of its matrices rejected (tile_kernels.hip "natural order or pivot search?")
     if (!SPD && tile_policy_use_pivot(sizeof(T) == 8, (n + 15) / 16))
         return n > 128 ? launch_gj_tileq<T>(n, A, X, batch, info, stream, nullptr, nullptr, nullptr, nullptr, nullptr)
                        : launch_gj_tilep4<T>(n, A, X, batch, info, stream);
     // [0], [1] = counts; [2 .. batch+2) = rejected matrices; [batch+2 ..) = (Gauss-Jordan) the singular ones among them; behind the
     // screening pass (r04, tile_screen.hpp: general batches under the default policy) [2 batch + 4] = count of the accepted matrices,
     // then their list
-    const int nt = (n + 15) / 16;
-    const bool screen = !SPD && tile_policy_use_screen(sizeof(T) == 8, nt);
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), ((screen ? 3 : 2) * batch + 6) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, 2 * sizeof(int), stream);
-    if (e == hipSuccess && screen) e = hipMemsetAsync(ws + 2 * batch + 4, 0, sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
-        return e;
-    }
-    int *const acc_count = ws + 2 * batch + 4, *const acc_list = ws + 2 * batch + 5;
-    const int *const in_count = screen ? acc_count : nullptr, *const in_list = screen ? acc_list : nullptr;
-    const unsigned resident = nt > 8 ? 256u : 256u * 3u;  // NT wavefronts per matrix: one workgroup per CU
-    const unsigned sgrid = (unsigned)(batch < 256u * 16u ? batch : 256u * 16u);  // screening: every resident wave takes many matrices
-    const unsigned grid = (unsigned)(batch < resident * tile_grid_rounds() ? batch : resident * tile_grid_rounds());
-    const unsigned b = (unsigned)batch;
-// more than 8 x 8 tiles: run-time n only, f64 up to 12 x 12
-#define T4_WIDE(NT_)                                                                                                  \
-    if constexpr ((sizeof(T) == 4 || NT_ <= 12) && (!SPD || NT_ >= (sizeof(T) == 8 ? 12 : 11))) {                                                             \
-        if constexpr (sizeof(T) == 8)                                                                                 \
-            hipLaunchKernelGGL((matinv_gj_tile4_f64<NT_, false, NT_, SPD>), dim3(grid), dim3(64 * NT_), 0, stream, A, X, info, n, b, ws, ws + 2, in_count, in_list); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((matinv_gj_tile4_f32<NT_, false, NT_, SPD>), dim3(grid), dim3(64 * NT_), 0, stream, A, X, info, n, b, ws, ws + 2, in_count, in_list); \
-    }
-#define T4_LAUNCH(NT_)                                                                                                \
-    if constexpr (SPD) {                                                                                              \
-        /* not instantiated: the lower-tile kernels serve every SPD n <= 128 (refused at the top of this function) */     \
-    } else if constexpr (sizeof(T) == 8) {                                                                                   \
-        if (n == 16 * NT_)                                                                                            \
-            hipLaunchKernelGGL((matinv_gj_tile4_f64<NT_, true, t4_waves(true, NT_), SPD>), dim3(grid), dim3(64 * t4_waves(true, NT_)), 0, stream, A, X, info, n, b, ws, ws + 2, in_count, in_list); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((matinv_gj_tile4_f64<NT_, false, t4_waves(true, NT_), SPD>), dim3(grid), dim3(64 * t4_waves(true, NT_)), 0, stream, A, X, info, n, b, ws, ws + 2, in_count, in_list); \
-    } else {                                                                                                          \
-        if (n == 16 * NT_)                                                                                            \
-            hipLaunchKernelGGL((matinv_gj_tile4_f32<NT_, true, t4_waves(false, NT_), SPD>), dim3(grid), dim3(64 * t4_waves(false, NT_)), 0, stream, A, X, info, n, b, ws, ws + 2, in_count, in_list); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((matinv_gj_tile4_f32<NT_, false, t4_waves(false, NT_), SPD>), dim3(grid), dim3(64 * t4_waves(false, NT_)), 0, stream, A, X, info, n, b, ws, ws + 2, in_count, in_list); \
-    }
-#define T4_SCREEN(NT_)                                                                                                \
-    if constexpr (!SPD && (sizeof(T) == 4 || NT_ <= 12)) {                                                            \
-        if constexpr (sizeof(T) == 8)                                                                                 \
-            hipLaunchKernelGGL((matinv_gj_tile4_screen_f64<NT_>), dim3(sgrid), dim3(64), 0, stream, A, n, b, ws, ws + 2, acc_count, acc_list); \
-        else                                                                                                          \
-            hipLaunchKernelGGL((matinv_gj_tile4_screen_f32<NT_>), dim3(sgrid), dim3(64), 0, stream, A, n, b, ws, ws + 2, acc_count, acc_list); \
-    }
-    if (screen) {
-        switch (nt) {
-        case 5: T4_SCREEN(5) break;
-        case 6: T4_SCREEN(6) break;
-        case 7: T4_SCREEN(7) break;
-        case 8: T4_SCREEN(8) break;
-        case 9: T4_SCREEN(9) break;
-        case 10: T4_SCREEN(10) break;
-        case 11: T4_SCREEN(11) break;
-        case 12: T4_SCREEN(12) break;
-        case 13: T4_SCREEN(13) break;
-        case 14: T4_SCREEN(14) break;
-        case 15: T4_SCREEN(15) break;
-        default: T4_SCREEN(16) break;
+    constexpr bool F64 = sizeof(T) == 8;
+    const TileShape s = tile_shape(n);
+    const bool screen = !SPD && tile_policy_use_screen(F64, s.nt);
+    return with_scratch_ints((screen ? 3 : 2) * batch + 6, 2, stream, [&](int *ws) {
+        int *const acc_count = ws + 2 * batch + 4, *const acc_list = ws + 2 * batch + 5;
+        if (screen) {
+            const hipError_t e = hipMemsetAsync(acc_count, 0, sizeof(int), stream);
+            if (e != hipSuccess) return e;
         }
-    }
-#undef T4_SCREEN
-    switch (nt) {
-    case 5: T4_LAUNCH(5) break;
-    case 6: T4_LAUNCH(6) break;
-    case 7: T4_LAUNCH(7) break;
-    case 8: T4_LAUNCH(8) break;
-    case 9: T4_WIDE(9) break;
-    case 10: T4_WIDE(10) break;
-    case 11: T4_WIDE(11) break;
-    case 12: T4_WIDE(12) break;
-    case 13: T4_WIDE(13) break;
-    case 14: T4_WIDE(14) break;
-    case 15: T4_WIDE(15) break;
-    default: T4_WIDE(16) break;
-    }
-#undef T4_LAUNCH
-#undef T4_WIDE
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-        if (SPD) {  // beyond 8 x 8 tiles the SPD kernel finishes its rejects itself
-            if (nt <= 8) e = launch_chol_lds_worklist<T>(n, A, X, ws, ws + 2, info, stream);
-        } else if (nt <= 8) {  // rejected = needs row exchanges: the PIVOTING kernel of this size, in the same stream
-            e = launch_gj_tilep4_worklist<T>(n, A, X, batch, ws, ws + 2, ws + 1, ws + 2 + batch, info, stream,
-                                             tile_policy_record(sizeof(T) == 8, nt, batch), screen);
-        } else {
-            e = launch_gj_tileq<T>(n, A, X, batch, info, stream, ws, ws + 2, tile_policy_record(sizeof(T) == 8, nt, batch), nullptr, nullptr);
-        }
-    }
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
+        const int *const in_count = screen ? acc_count : nullptr, *const in_list = screen ? acc_list : nullptr;
+        // NT wavefronts per matrix beyond 8 x 8 tiles: one workgroup per CU
+        const unsigned grid = tile_grid(batch, s.nt > 8 ? 1u : 3u), b = (unsigned)batch;
+        const unsigned sgrid = tile_grid(batch, 16u, 1u);  // screening: every resident wave takes many matrices
+        if (screen)
+            with_nt<5, 16>(s.nt, [&](auto NT) {
+                if constexpr (!SPD && F64 && NT <= 12)
+                    hipLaunchKernelGGL((matinv_gj_tile4_screen_f64<NT>), dim3(sgrid), dim3(64), 0, stream, A, n, b, ws, ws + 2, acc_count, acc_list);
+                else if constexpr (!SPD && !F64)
+                    hipLaunchKernelGGL((matinv_gj_tile4_screen_f32<NT>), dim3(sgrid), dim3(64), 0, stream, A, n, b, ws, ws + 2, acc_count, acc_list);
+            });
+        with_tile<5, 16>(s, [&](auto NT, auto FULL) {
+            if constexpr (NT <= 8) {
+                // SPD: not instantiated, the lower-tile kernels serve every SPD n <= 128 (refused at the top of this function)
+                constexpr int W = t4_waves(F64, NT);
+                if constexpr (!SPD && F64)
+                    hipLaunchKernelGGL((matinv_gj_tile4_f64<NT, FULL, W, SPD>), dim3(grid), dim3(64 * W), 0, stream, A, X, info, n, b, ws, ws + 2,
+                                       in_count, in_list);
+                else if constexpr (!SPD)
+                    hipLaunchKernelGGL((matinv_gj_tile4_f32<NT, FULL, W, SPD>), dim3(grid), dim3(64 * W), 0, stream, A, X, info, n, b, ws, ws + 2,
+                                       in_count, in_list);
+            } else if constexpr ((!F64 || NT <= 12) && (!SPD || NT >= (F64 ? 12 : 11))) {
+                // more than 8 x 8 tiles: run-time n only, f64 up to 12 x 12
+                if constexpr (F64)
+                    hipLaunchKernelGGL((matinv_gj_tile4_f64<NT, false, NT, SPD>), dim3(grid), dim3(64 * NT), 0, stream, A, X, info, n, b, ws, ws + 2,
+                                       in_count, in_list);
+                else
+                    hipLaunchKernelGGL((matinv_gj_tile4_f32<NT, false, NT, SPD>), dim3(grid), dim3(64 * NT), 0, stream, A, X, info, n, b, ws, ws + 2,
+                                       in_count, in_list);
+            }
+        });
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (SPD)  // beyond 8 x 8 tiles the SPD kernel finishes its rejects itself
+            return s.nt <= 8 ? launch_chol_lds_worklist<T>(n, A, X, ws, ws + 2, info, stream) : hipSuccess;
+        if (s.nt <= 8)  // rejected = needs row exchanges: the PIVOTING kernel of this size, in the same stream
+            return launch_gj_tilep4_worklist<T>(n, A, X, batch, ws, ws + 2, ws + 1, ws + 2 + batch, info, stream,
+                                                tile_policy_record(F64, s.nt, batch), screen);
+        return launch_gj_tileq<T>(n, A, X, batch, info, stream, ws, ws + 2, tile_policy_record(F64, s.nt, batch), nullptr, nullptr);
+    });
 }
 
 template <class T>

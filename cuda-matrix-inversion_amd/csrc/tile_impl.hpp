@@ -1,7 +1,11 @@
-// tile_kernels.inc (compiled in parts selected with MATINV_TILE_PART so that they build in parallel: tile_kernels.hip = the fp64 SPD / fused-pipeline
-// kernels + the family's non-template helpers, tile_f32_kernels.hip = their fp32 half, tile_gj_kernels.hip / tile_gj_f32_kernels.hip = the natural-order
-// Gauss-Jordan kernels, spd_wide_* / gp_spd_wide_* = the widest one-wavefront symmetric sweeps) -- kernel family "TILE": one matrix per wavefront, register-resident in 16x16 fp64 MFMA
-// accumulator tiles (v_mfma_f64_16x16x4_f64), for 16 < n <= 64 (n is padded to NT*16 with an identity block).
+// tile_impl.hpp -- device code of kernel family "TILE": one matrix per wavefront, register-resident in 16x16 fp64 MFMA
+// accumulator tiles (v_mfma_f64_16x16x4_f64), for 16 < n <= 64 (n is padded to NT*16 with an identity block), and the symmetric
+// sweep on lower tiles that serves the Cholesky entry point and the fused mean / variance up to 7 x 7 (fp64) / 10 x 10 (fp32) tiles.
+// The translation units that instantiate it, one group of kernels each so that they build in parallel: tile_gj_kernels.hip /
+// tile_gj_f32_kernels.hip = the natural-order Gauss-Jordan kernels, tile_kernels.hip / tile_f32_kernels.hip = the symmetric sweeps
+// (tile_kernels.hip also holds the family's non-template helpers), tile_big_f32_kernels.hip, spd_wide_* / gp_spd_wide_* = the widest
+// one-wavefront symmetric sweeps.
+#pragma once
 //
 // Why MFMA for an inversion: Gauss-Jordan is a sequence of rank-1 updates whose cost on the VALU is dominated by
 // BROADCASTING the multiplier column / pivot row across the wavefront (2 v_readlane per fp64 value per step).
@@ -413,80 +417,6 @@ __global__ __launch_bounds__(64, FULL ? 4 : 3) void matinv_gj_tile_f32(BatchRef<
     gj_tile_body<float, NT, FULL, LOOKAHEAD, EARLY>(Ain, Xout, info, n_rt, batch, work_count, work_list, panel, in_count, in_list);
 }
 
-// The natural-order pass of the Gauss-Jordan entry point for n <= 64 (default policy): [screen +] verified natural-order kernel, then
-// the pivoting kernel over the matrices they rejected, all in `stream`. ws: [0] rejected, [1] singular, [2] accepted (screened launches),
-// [4 .. 4+batch) rejected matrices, then the singular ones among them, then the accepted ones.
-bool tile_policy_use_screen(bool f64, int nt);
-template <class T>
-static hipError_t launch_gj_tile_natural(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
-{
-    constexpr bool F64 = sizeof(T) == 8;
-    const int nt = (n + 15) / 16;
-    const bool rowlane2 = rowlane2_natural_use(F64, n);
-    const bool screen = !rowlane2 && tile_policy_use_screen(F64, nt);
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), ((screen ? 3 : 2) * batch + 4) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, 4 * sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
-        return e;
-    }
-    int *const rej_count = ws, *const sing_count = ws + 1, *const acc_count = ws + 2;
-    int *const rej_list = ws + 4, *const sing_list = ws + 4 + batch, *const acc_list = ws + 4 + 2 * batch;
-    // grid-stride over the batch: enough waves to fill 256 CUs several times over, few enough to amortise setup
-    const unsigned per_cu = F64 ? 8u : 16u;
-    const unsigned grid = (unsigned)(batch < 256u * per_cu * tile_grid_rounds() ? batch : 256u * per_cu * tile_grid_rounds());
-    const unsigned b = (unsigned)batch;
-    const int *in_count = screen ? acc_count : nullptr, *in_list = screen ? acc_list : nullptr;
-    const unsigned sgrid = (unsigned)(batch < 256u * 16u ? batch : 256u * 16u);  // screening: every resident wave takes many matrices
-#define TILE_LAUNCH2(NT_, EARLY_)                                                                                     \
-    do {                                                                                                              \
-        if constexpr (F64) {                                                                                          \
-            if (screen && n == 16 * NT_)                                                                              \
-                hipLaunchKernelGGL((matinv_gj_tile_screen_f64<NT_, true>), dim3(sgrid), dim3(64), 0, stream, A, n, b, rej_count, rej_list, acc_count, acc_list); \
-            else if (screen)                                                                                          \
-                hipLaunchKernelGGL((matinv_gj_tile_screen_f64<NT_, false>), dim3(sgrid), dim3(64), 0, stream, A, n, b, rej_count, rej_list, acc_count, acc_list); \
-            if (n == 16 * NT_)                                                                                        \
-                hipLaunchKernelGGL((matinv_gj_tile_f64<NT_, true, true, (EARLY_) && NT_ >= 3>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count, rej_list, in_count, in_list); \
-            else                                                                                                      \
-                hipLaunchKernelGGL((matinv_gj_tile_f64<NT_, false, true, (EARLY_) && NT_ >= 3>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count, rej_list, in_count, in_list); \
-        } else {                                                                                                      \
-            if (screen && n == 16 * NT_)                                                                              \
-                hipLaunchKernelGGL((matinv_gj_tile_screen_f32<NT_, true>), dim3(sgrid), dim3(64), 0, stream, A, n, b, rej_count, rej_list, acc_count, acc_list); \
-            else if (screen)                                                                                          \
-                hipLaunchKernelGGL((matinv_gj_tile_screen_f32<NT_, false>), dim3(sgrid), dim3(64), 0, stream, A, n, b, rej_count, rej_list, acc_count, acc_list); \
-            if (n == 16 * NT_)                                                                                        \
-                hipLaunchKernelGGL((matinv_gj_tile_f32<NT_, true, true, (EARLY_) && NT_ >= 3>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count, rej_list, in_count, in_list); \
-            else                                                                                                      \
-                hipLaunchKernelGGL((matinv_gj_tile_f32<NT_, false, true, (EARLY_) && NT_ >= 3>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count, rej_list, in_count, in_list); \
-        }                                                                                                             \
-    } while (0)
-    // behind the screening pass the natural-order kernel takes its early-exit instantiation (NT >= 3; see gj_tile_body)
-#define TILE_LAUNCH(NT_)                                                                                              \
-    do {                                                                                                              \
-        if (screen) TILE_LAUNCH2(NT_, true);                                                                          \
-        else TILE_LAUNCH2(NT_, false);                                                                                \
-    } while (0)
-    if (rowlane2) {
-        e = enqueue_gj_rowlane2<T>(n, A, X, batch, info, stream, rej_count, rej_list);
-    } else {
-        switch (nt) {
-        case 1: TILE_LAUNCH(1); break;
-        case 2: TILE_LAUNCH(2); break;
-        case 3: TILE_LAUNCH(3); break;
-        default: TILE_LAUNCH(4); break;
-        }
-        e = hipGetLastError();
-    }
-#undef TILE_LAUNCH
-#undef TILE_LAUNCH2
-    if (e == hipSuccess)
-        e = launch_gj_tilep_worklist<T>(n, A, X, batch, rej_count, rej_list, sing_count, sing_list, info, stream, tile_policy_record(F64, nt, batch), screen);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
-}
-
 // ================================================================================================================
 // SPD inputs: symmetric blocked sweep on LOWER-TRIANGULAR tile storage (the square-root-free member of the Cholesky
 // family: the same Schur complements as A = L L^T, pivots = squares of the Cholesky diagonal, no pivot search needed
@@ -771,449 +701,105 @@ __global__ __launch_bounds__(64, NT >= 9 ? MATINV_SPD_WIDE_OCC : 2) void matinv_
     spd_tile_body<float, NT, false, true>(A, X, info, n_rt, batch, work_count, work_list, panel, SpdGp<float>{As, Cs, Ds, Es, out});
 }
 
-// ------------------------------------------------------------------------------------------------
+// ---- launchers shared by the fp64 and fp32 translation units (explicitly instantiated there) -----------------------------------
+
+// The natural-order pass of the Gauss-Jordan entry point for n <= 64 (default policy): [screen +] verified natural-order kernel, then
+// the pivoting kernel over the matrices they rejected, all in `stream`. ws: [0] rejected, [1] singular, [2] accepted (screened launches),
+// [4 .. 4+batch) rejected matrices, then the singular ones among them, then the accepted ones.
+bool tile_policy_use_screen(bool f64, int nt);
 template <class T>
-bool tile_family_supports(int n);
-template <class T>
-hipError_t launch_gj_tile(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream);
-template <class T>
-bool spd_tile_supports(int n);
-template <class T>
-hipError_t launch_spd_tile(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream);
-// explicit specialisations, defined in the part named in the comment
-template <>
-bool tile_family_supports<double>(int n);  // 64
-template <>
-bool tile_family_supports<float>(int n);   // 64
-template <>
-bool spd_tile_supports<double>(int n);     // 64
-template <>
-bool spd_tile_supports<float>(int n);      // 64
-
-#if MATINV_TILE_PART == 64
-// r03: ONE wavefront per matrix beyond what 256 registers hold. A gfx950 wave may own up to 512 registers -- 256 VGPRs + 256
-// AGPRs, one file, and MFMA accumulates in AGPRs directly -- when its kernel asks for one wave per SIMD: hipcc then keeps the
-// accumulator tiles in AGPRs (fp64 7 x 7 lower tiles: 190 VGPRs + 224 AGPRs, no scratch). Four matrices per CU, no workgroup barrier,
-// no panel solve repeated per wave; r01/r02 stopped the one-wave kernels at 256 registers (two waves per SIMD) and went to several
-// wavefronts per matrix from there.
-
-// Measured at 100 k x 64^2 f64: 1 / 4 / 16 / 64 rounds -> 1.631 / 1.600 / 1.579 / 1.570 ms per launch: the hardware
-// dispatcher balances better than a static stride does, so the grids are (nearly) one workgroup per matrix and the stride
-// loop only matters for batches beyond 64 rounds.
-unsigned tile_grid_rounds()
+hipError_t launch_gj_tile_natural(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
 {
-    static const unsigned rounds = []() {
-        const char *s = getenv("MATINV_TILE_GRID_MULT");
-        const int v = s && *s ? atoi(s) : 64;
-        return (unsigned)(v < 1 ? 1 : v);
-    }();
-    return rounds;
-}
-
-// ---- natural order or pivot search? -------------------------------------------------------------------------------------
-// The verified-natural-order kernel is the fast path for diagonally dominant / SPD batches (0.50 of HBM at 64 x 64); a matrix
-// that fails its acceptance test is redone by the pivoting kernel in the same stream. Three policies (matinv_set_gj_policy,
-// MATINV_GJ_POLICY=natural|pivot|adaptive):
-//   NATURAL_FIRST (default since r03): every launch runs the natural-order kernel, rejects go to the pivoting kernel. What a
-//       matrix's result is depends on that matrix alone -- no launch history, no batch mates: the same call gives the same
-//       bits again, and a sharded batch the bits of the single launch. A batch of GENERAL matrices pays both kernels.
-//   PIVOT: every launch goes straight to the pivoting kernel (equally deterministic; what the reference's LU entry points,
-//       inverse_lu_cuda_batched_*, take: partial pivoting is their contract, src/gauss/inverse_gpu.cu:16-58).
-//   ADAPTIVE (r02 behaviour, opt-in): per (device, dtype, tile count) the launcher remembers how the LAST natural-order launch
-//       that has completed went -- (rejected, batch) come back as ONE 8-byte store of the work-list kernel into pinned host
-//       memory, never waited for -- and sends a batch straight to the pivoting kernel while at least a quarter of that launch
-//       was rejected; every 32nd launch in that state probes the natural order again. Fastest for callers that alternate
-//       rarely; a matrix that the natural-order kernel would accept although partial pivoting would move rows gets the
-//       pivoting kernel's bits or the natural ones depending on what ran before.
-// All of the state is per device and atomic: host threads driving different devices (or one device) do not race on it.
-namespace {
-constexpr int kMaxDevices = 16, kSlotsPerDevice = 64;
-struct HintSlot {
-    std::atomic<unsigned long long> pair;       // (batch << 32) | rejected of the last completed natural-order launch: device store
-    std::atomic<unsigned> launches_in_pivot_mode;
-};
-HintSlot *hint_slots()
-{
-    static HintSlot *slots = []() -> HintSlot * {
-        void *p = nullptr;
-        if (hipHostMalloc(&p, sizeof(HintSlot) * kMaxDevices * kSlotsPerDevice, hipHostMallocPortable) != hipSuccess) return nullptr;
-        memset(p, 0, sizeof(HintSlot) * kMaxDevices * kSlotsPerDevice);
-        return static_cast<HintSlot *>(p);
-    }();
-    return slots;
-}
-std::atomic<int> g_policy{-1};  // -1: not read from the environment yet
-std::atomic<unsigned long long> g_natural_launches{0}, g_pivot_launches{0};
-std::atomic<int> g_last_slot{0};
-int slot_index(bool f64, int nt)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-    return (dev % kMaxDevices) * kSlotsPerDevice + (f64 ? 32 : 0) + (nt & 31);
-}
-}  // namespace
-
-int gj_policy()
-{
-    int v = g_policy.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *s = getenv("MATINV_GJ_POLICY");
-        v = MATINV_GJ_NATURAL_FIRST;
-        if (s && !strcmp(s, "pivot")) v = MATINV_GJ_PIVOT;
-        else if (s && !strcmp(s, "adaptive")) v = MATINV_GJ_ADAPTIVE;
-        int expected = -1;
-        if (!g_policy.compare_exchange_strong(expected, v)) v = expected;  // somebody set it meanwhile
-    }
-    return v;
-}
-
-int set_gj_policy(int policy)
-{
-    const int old = gj_policy();
-    g_policy.store(policy, std::memory_order_relaxed);
-    return old;
-}
-
-bool tile_policy_use_pivot(bool f64, int nt)
-{
-    const int pol = gj_policy();
-    bool pivot = pol == MATINV_GJ_PIVOT;
-    if (pol == MATINV_GJ_ADAPTIVE) {
-        HintSlot *h = hint_slots();
-        const int idx = slot_index(f64, nt);
-        g_last_slot.store(idx, std::memory_order_relaxed);
-        if (h) {
-            const unsigned long long pr = h[idx].pair.load(std::memory_order_relaxed);
-            const unsigned long long batch = pr >> 32, rejected = pr & 0xffffffffull;
-            if (batch > 0 && 4ull * rejected >= batch)
-                pivot = ((h[idx].launches_in_pivot_mode.fetch_add(1, std::memory_order_relaxed) + 1) % 32u) != 0;  // every 32nd probes
+    constexpr bool F64 = sizeof(T) == 8;
+    const TileShape s = tile_shape(n);
+    const bool rowlane2 = rowlane2_natural_use(F64, n);
+    const bool screen = !rowlane2 && tile_policy_use_screen(F64, s.nt);
+    return with_scratch_ints((screen ? 3 : 2) * batch + 4, 4, stream, [&](int *ws) {
+        int *const rej_count = ws, *const sing_count = ws + 1, *const acc_count = ws + 2;
+        int *const rej_list = ws + 4, *const sing_list = ws + 4 + batch, *const acc_list = ws + 4 + 2 * batch;
+        hipError_t e;
+        if (rowlane2) {
+            e = enqueue_gj_rowlane2<T>(n, A, X, batch, info, stream, rej_count, rej_list);
+        } else {
+            // grid-stride over the batch: enough waves to fill 256 CUs several times over, few enough to amortise setup
+            const unsigned grid = tile_grid(batch, F64 ? 8u : 16u), b = (unsigned)batch;
+            const unsigned sgrid = tile_grid(batch, 16u, 1u);  // screening: every resident wave takes many matrices
+            with_tile<1, 4>(s, [&](auto NT, auto FULL) {
+                // behind the screening pass the natural-order kernel takes its early-exit instantiation (NT >= 3; see gj_tile_body)
+                constexpr bool EARLY = NT >= 3;
+                if constexpr (F64) {
+                    if (!screen) {
+                        hipLaunchKernelGGL((matinv_gj_tile_f64<NT, FULL, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count,
+                                           rej_list, nullptr, nullptr);
+                        return;
+                    }
+                    hipLaunchKernelGGL((matinv_gj_tile_screen_f64<NT, FULL>), dim3(sgrid), dim3(64), 0, stream, A, n, b, rej_count, rej_list,
+                                       acc_count, acc_list);
+                    hipLaunchKernelGGL((matinv_gj_tile_f64<NT, FULL, true, EARLY>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count,
+                                       rej_list, acc_count, acc_list);
+                } else {
+                    if (!screen) {
+                        hipLaunchKernelGGL((matinv_gj_tile_f32<NT, FULL, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count,
+                                           rej_list, nullptr, nullptr);
+                        return;
+                    }
+                    hipLaunchKernelGGL((matinv_gj_tile_screen_f32<NT, FULL>), dim3(sgrid), dim3(64), 0, stream, A, n, b, rej_count, rej_list,
+                                       acc_count, acc_list);
+                    hipLaunchKernelGGL((matinv_gj_tile_f32<NT, FULL, true, EARLY>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, rej_count,
+                                       rej_list, acc_count, acc_list);
+                }
+            });
+            e = hipGetLastError();
         }
-    }
-    (pivot ? g_pivot_launches : g_natural_launches).fetch_add(1, std::memory_order_relaxed);
-    return pivot;
+        if (e == hipSuccess)
+            e = launch_gj_tilep_worklist<T>(n, A, X, batch, rej_count, rej_list, sing_count, sing_list, info, stream,
+                                            tile_policy_record(F64, s.nt, batch), screen);
+        return e;
+    });
 }
-
-// before a natural-order launch: where the work-list kernel that follows it in the stream stores (batch << 32) | rejected
-// (pinned host memory, one 8-byte store, never waited for), or nullptr when nobody reads it
-hint_t *tile_policy_record(bool f64, int nt, size_t batch)
-{
-    (void)batch;
-    if (gj_policy() == MATINV_GJ_PIVOT) return nullptr;
-    HintSlot *h = hint_slots();
-    if (!h) return nullptr;
-    static_assert(sizeof(std::atomic<unsigned long long>) == sizeof(hint_t), "the device stores into the atomic's storage");
-    return reinterpret_cast<hint_t *>(&h[slot_index(f64, nt)].pair);
-}
-
-// NATURAL_FIRST: run the screening kernel (gj_tile_screen_body) in front of the natural-order kernel? Yes while the last completed
-// natural-order launch of this class rejected at least a quarter of its batch. It changes what a launch costs, never what it
-// computes. MATINV_TILE_SCREEN=0 / 1: never / always (tests, A/B).
-bool tile_policy_use_screen(bool f64, int nt)
-{
-    static const int forced = []() {
-        const char *s = getenv("MATINV_TILE_SCREEN");
-        return !s || !*s ? -1 : (*s == '0' ? 0 : 1);
-    }();
-    if (forced >= 0) return forced == 1;
-    if (gj_policy() != MATINV_GJ_NATURAL_FIRST) return false;
-    HintSlot *h = hint_slots();
-    if (!h) return false;
-    const unsigned long long pr = h[slot_index(f64, nt)].pair.load(std::memory_order_relaxed);
-    const unsigned long long batch = pr >> 32, rejected = pr & 0xffffffffull;
-    return batch > 0 && 4ull * rejected >= batch;
-}
-
-TileStats tile_stats()
-{
-    HintSlot *h = hint_slots();
-    TileStats t{g_natural_launches.load(), g_pivot_launches.load(), 0, 0};
-    if (h) {
-        const unsigned long long pr = h[g_last_slot.load()].pair.load(std::memory_order_relaxed);
-        t.last_rejected = pr & 0xffffffffull;
-        t.last_batch = pr >> 32;
-    }
-    return t;
-}
-
-template <>
-bool tile_family_supports<double>(int n) { return n >= 1 && n <= 192; }  // 64 < n: tile4_kernels.hip (up to 12 x 12 tiles)
-template <>
-bool tile_family_supports<float>(int n) { return n >= 1 && n <= 256; }
-
-
-template <>
-bool spd_tile_supports<double>(int n) { return n >= 1 && n <= 192; }  // 64 < n: tile4_kernels.hip (up to 12 x 12 tiles)
-template <>
-bool spd_tile_supports<float>(int n) { return n >= 1 && n <= 256; }
-
-#endif
-
-// fused pipeline on the SPD sweep: f64 80 < n <= 96 (6 x 6 tiles), f32 96 < n <= 112 (7 x 7); rejects (not SPD) -> LDS pipeline
-#if MATINV_TILE_PART == 64
-// largest n the ONE-wavefront symmetric sweep takes: fp64 7 x 7 lower tiles (224 accumulator registers, VGPRs + AGPRs, one wave
-// per SIMD); fp32 10 x 10 (55 tiles = 220 registers, one wave per SIMD; 11 x 11 = 264: 2 KB of scratch per lane)
-int spd_onewave_max(bool f64) { return f64 ? 112 : 160; }
-bool gp_spd_tile_supports(bool f64, int n) { return n > (f64 ? 80 : 96) && n <= spd_onewave_max(f64); }
-#endif
 
 template <class T>
-static hipError_t launch_gp_spd_tile_impl(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
-                                          int *info, hipStream_t stream)
+hipError_t launch_gj_tile(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
 {
-    if (!gp_spd_tile_supports(sizeof(T) == 8, n)) return hipErrorInvalidValue;
-    if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
-        return e;
-    }
-    const unsigned grid = (unsigned)(batch < 256u * 8u * tile_grid_rounds() ? batch : 256u * 8u * tile_grid_rounds());
-    const unsigned b = (unsigned)batch;
-    if constexpr (sizeof(T) == 8) {
-        if (n <= 96) hipLaunchKernelGGL((matinv_gp_spd_tile_f64<6>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
-        else e = enqueue_gp_spd_tile_wide_f64(n, As, Bs, Cs, Ds, Es, out, grid, b, info, ws, stream);
-    } else {
-        if (n <= 112) hipLaunchKernelGGL((matinv_gp_spd_tile_f32<7>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
-        else if (n <= 128) hipLaunchKernelGGL((matinv_gp_spd_tile_f32<8>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
-        else e = enqueue_gp_spd_tile_wide_f32(n, As, Bs, Cs, Ds, Es, out, grid, b, info, ws, stream);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = launch_gp_lds_worklist<T>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
-}
-
-// fp32, 7 x 7 and 8 x 8 lower tiles on one wavefront (Cholesky entry point; the fused pipeline of those sizes): tile_big_f32_kernels.hip
-hipError_t enqueue_spd_tile_big_f32(int n, BatchRef<const float> A, BatchRef<float> X, unsigned grid, unsigned b, int *info, int *ws,
-                                    hipStream_t stream);
-#if MATINV_TILE_PART == 35
-template <>
-hipError_t launch_gp_spd_tile<float>(int n, const float *As, const float *Bs, const float *Cs, const float *Ds, const float *Es, float *out,
-                                     size_t batch, int *info, hipStream_t stream)
-{
-    return launch_gp_spd_tile_impl<float>(n, As, Bs, Cs, Ds, Es, out, batch, info, stream);
-}
-
-hipError_t enqueue_spd_tile_big_f32(int n, BatchRef<const float> A, BatchRef<float> X, unsigned grid, unsigned b, int *info, int *ws,
-                                    hipStream_t stream)
-{
-    if (n == 112) hipLaunchKernelGGL((matinv_spd_tile_f32<7, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1);
-    else if (n <= 112) hipLaunchKernelGGL((matinv_spd_tile_f32<7, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1);
-    // 8 x 8: the run-time-n instantiation also for n = 128 (the compile-time-n one measured 2.3e6 inv/s against 2.1e7)
-    else hipLaunchKernelGGL((matinv_spd_tile_f32<8, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1);
-    return hipGetLastError();
-}
-#endif
-#if MATINV_TILE_PART == 36  // tile_gj_f32_kernels.hip: the natural-order Gauss-Jordan kernels by themselves (build time)
-template <>
-hipError_t launch_gj_tile<float>(int n, BatchRef<const float> A, BatchRef<float> X, size_t batch, int *info,
-                                 hipStream_t stream)
-{
-    if (!tile_family_supports<float>(n)) return hipErrorInvalidValue;
-    if (n > 64) return launch_gj_tile4<float>(n, A, X, batch, info, stream);
-    if (batch == 0) return hipSuccess;
-    if (tile_policy_use_pivot(false, (n + 15) / 16)) return launch_gj_tilep<float>(n, A, X, batch, info, stream);
-    return launch_gj_tile_natural<float>(n, A, X, batch, info, stream);
-}
-#endif
-#if MATINV_TILE_PART == 32
-
-template <>
-hipError_t launch_spd_tile<float>(int n, BatchRef<const float> A, BatchRef<float> X, size_t batch, int *info,
-                                  hipStream_t stream)
-{
-    if (!spd_tile_supports<float>(n)) return hipErrorInvalidValue;
-    // one wavefront holds the lower triangle up to 7 x 7 tiles at two waves per SIMD, 8 x 8 (144 accumulator registers) since r03,
-    // and 9 x 9 / 10 x 10 (180 / 220) at one wave per SIMD with VGPR-form MFMAs and AGPR parking space (spd_wide_f32_kernels.hip)
-    if (n > spd_onewave_max(false)) return launch_spd_tile4<float>(n, A, X, batch, info, stream);
-    if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
-        return e;
-    }
-    const int nt = (n + 15) / 16;
-    const unsigned grid = (unsigned)(batch < 256u * 16u * tile_grid_rounds() ? batch : 256u * 16u * tile_grid_rounds());
-    const unsigned b = (unsigned)batch;
-#define SPD_LAUNCH_F32(NT_)                                                                                           \
-    if (n == 16 * NT_)                                                                                                \
-        hipLaunchKernelGGL((matinv_spd_tile_f32<NT_, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1); \
-    else                                                                                                              \
-        hipLaunchKernelGGL((matinv_spd_tile_f32<NT_, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1)
-    switch (nt) {
-    case 1: SPD_LAUNCH_F32(1); break;
-    case 2: SPD_LAUNCH_F32(2); break;
-    case 3: SPD_LAUNCH_F32(3); break;
-    case 4: SPD_LAUNCH_F32(4); break;
-    case 5: SPD_LAUNCH_F32(5); break;
-    case 6: SPD_LAUNCH_F32(6); break;
-    case 7:
-    case 8: e = enqueue_spd_tile_big_f32(n, A, X, grid, b, info, ws, stream); break;
-    default: e = enqueue_spd_tile_wide_f32(n, A, X, grid, b, info, ws, stream); break;
-    }
-#undef SPD_LAUNCH_F32
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = launch_chol_lds_worklist<float>(n, A, X, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
-}
-
-#endif
-
-#if MATINV_TILE_PART == 33
-// fp32 symmetric sweep of 9 x 9 / 10 x 10 lower tiles on ONE wavefront (128 < n <= 160), run-time n only; translation units of
-// their own (spd_wide_f32_kernels.hip, gp_spd_wide_f32_kernels.hip): each fully unrolled instantiation takes over a minute to compile
-hipError_t enqueue_spd_tile_wide_f32(int n, BatchRef<const float> A, BatchRef<float> X, unsigned grid, unsigned b, int *info, int *ws,
-                                     hipStream_t stream)
-{
-    switch ((n + 15) / 16) {
-    case 9: hipLaunchKernelGGL((matinv_spd_tile_f32<9, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1); break;
-    case 10: hipLaunchKernelGGL((matinv_spd_tile_f32<10, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#endif
-#if MATINV_TILE_PART == 34
-hipError_t enqueue_gp_spd_tile_wide_f32(int n, const float *As, const float *Bs, const float *Cs, const float *Ds, const float *Es, float *out,
-                                        unsigned grid, unsigned b, int *info, int *ws, hipStream_t stream)
-{
-    switch ((n + 15) / 16) {
-    case 9: hipLaunchKernelGGL((matinv_gp_spd_tile_f32<9>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); break;
-    case 10: hipLaunchKernelGGL((matinv_gp_spd_tile_f32<10>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#endif
-
-#if MATINV_TILE_PART == 65
-// fp64 symmetric sweep of 7 x 7 lower tiles on ONE wavefront (96 < n <= 112; 224 accumulator registers, one wave per SIMD): a translation
-// unit of its own (spd_wide_f64_kernels.hip) so that it can be compiled with VGPR-form MFMAs and the AGPRs as parking space -- with
-// hipcc's default AGPR-form MFMAs the same kernels are correct here (256-bit results never overlap their C operand) but slower:
-// Cholesky 112^2 1.36e7 -> 1.59e7 inv/s, pipeline 1.42e7 -> 1.48e7 items/s
-hipError_t enqueue_spd_tile_wide_f64(int n, BatchRef<const double> A, BatchRef<double> X, unsigned grid, unsigned b, int *info, int *ws,
-                                     hipStream_t stream)
-{
-    if (n == 112) hipLaunchKernelGGL((matinv_spd_tile_f64<7, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1);
-    else hipLaunchKernelGGL((matinv_spd_tile_f64<7, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1);
-    return hipGetLastError();
-}
-hipError_t enqueue_gp_spd_tile_wide_f64(int n, const double *As, const double *Bs, const double *Cs, const double *Ds, const double *Es,
-                                        double *out, unsigned grid, unsigned b, int *info, int *ws, hipStream_t stream)
-{
-    hipLaunchKernelGGL((matinv_gp_spd_tile_f64<7>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
-    return hipGetLastError();
-}
-#endif
-
-#if MATINV_TILE_PART == 64
-template <>
-hipError_t launch_gp_spd_tile<double>(int n, const double *As, const double *Bs, const double *Cs, const double *Ds, const double *Es,
-                                      double *out, size_t batch, int *info, hipStream_t stream)
-{
-    return launch_gp_spd_tile_impl<double>(n, As, Bs, Cs, Ds, Es, out, batch, info, stream);
-}
-
-#endif
-#if MATINV_TILE_PART == 66  // tile_gj_kernels.hip
-template <>
-hipError_t launch_gj_tile<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, int *info,
-                                  hipStream_t stream)
-{
-    if (!tile_family_supports<double>(n)) return hipErrorInvalidValue;
+    if (!tile_family_supports<T>(n)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
     // (r03, measured and not kept: the natural-order sweep of 5 x 5 / 6 x 6 tiles on ONE wavefront with the accumulators in AGPRs,
     // one wave per SIMD -- 2.6e7 / 2.5e7 inv/s at 72^2 / 80^2, the same as two wavefronts per matrix, and 1.7e7 against 2.0e7 at
     // 96^2, 1.2e7 against 2.1e7 at 88^2 (ragged: 720 B of scratch). All n^2 tiles instead of the lower triangle: with one wave
     // per SIMD nothing hides the panel solve between the MFMAs. The symmetric sweep, half the tiles, does gain: launch_spd_tile.)
-    if (n > 64) return launch_gj_tile4<double>(n, A, X, batch, info, stream);
-    if (tile_policy_use_pivot(true, (n + 15) / 16)) return launch_gj_tilep<double>(n, A, X, batch, info, stream);
-    return launch_gj_tile_natural<double>(n, A, X, batch, info, stream);
+    if (n > 64) return launch_gj_tile4<T>(n, A, X, batch, info, stream);
+    if (tile_policy_use_pivot(sizeof(T) == 8, tile_shape(n).nt)) return launch_gj_tilep<T>(n, A, X, batch, info, stream);
+    return launch_gj_tile_natural<T>(n, A, X, batch, info, stream);
 }
-#endif
-#if MATINV_TILE_PART == 64
 
-template <>
-hipError_t launch_spd_tile<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, int *info,
-                                   hipStream_t stream)
+// The instantiation of the one-wavefront symmetric sweep that serves n: FULL except for the fp32 kernels of 8 x 8 tiles and more, which
+// take run-time n only (the compile-time-n one measured 2.3e6 inv/s against 2.1e7 at 128^2)
+constexpr TileShape spd_tile_shape(bool f64, int n) { return {(n + 15) / 16, n % 16 == 0 && (f64 || n < 128)}; }
+
+// fused pipeline on the SPD sweep: f64 80 < n <= 96 (6 x 6 tiles), f32 96 < n <= 112 (7 x 7); rejects (not SPD) -> LDS pipeline
+hipError_t enqueue_spd_tile_big_f32(int n, BatchRef<const float> A, BatchRef<float> X, unsigned grid, unsigned b, int *info, int *ws,
+                                    hipStream_t stream);
+template <class T>
+hipError_t launch_gp_spd_tile(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch, int *info,
+                              hipStream_t stream)
 {
-    if (!spd_tile_supports<double>(n)) return hipErrorInvalidValue;
-    // one wavefront holds the lower triangle up to 6 x 6 tiles in 256 registers (two waves per SIMD) and 7 x 7 in VGPRs + AGPRs
-    // (one wave per SIMD, r03; before that 7 x 7 spilled: 5.8e6 inv/s at 112 x 112 against 9.9e6 on four wavefronts)
-    if (spd_tile2_supports(true, n)) return launch_spd_tile2(n, A, X, batch, info, stream);  // 112 < n <= 128: two waves, lower tiles
-    if (n > 112) return launch_spd_tile4<double>(n, A, X, batch, info, stream);  // 176 < n <= 192: one wavefront per tile column
+    if (!gp_spd_tile_supports(sizeof(T) == 8, n)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
-        return e;
-    }
-    const int nt = (n + 15) / 16;
-    const unsigned grid = (unsigned)(batch < 256u * 12u * tile_grid_rounds() ? batch : 256u * 12u * tile_grid_rounds());
-    const unsigned b = (unsigned)batch;
-#define SPD_LAUNCH(NT_)                                                                                               \
-    if (n == 16 * NT_)                                                                                                \
-        hipLaunchKernelGGL((matinv_spd_tile_f64<NT_, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1); \
-    else                                                                                                              \
-        hipLaunchKernelGGL((matinv_spd_tile_f64<NT_, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, ws, ws + 1)
-    switch (nt) {
-    case 1: SPD_LAUNCH(1); break;
-    case 2: SPD_LAUNCH(2); break;
-    case 3: SPD_LAUNCH(3); break;
-    case 4: SPD_LAUNCH(4); break;
-    case 5: SPD_LAUNCH(5); break;
-    case 6: SPD_LAUNCH(6); break;
-    default: e = enqueue_spd_tile_wide_f64(n, A, X, grid, b, info, ws, stream); break;  // 7 x 7: spd_wide_f64_kernels.hip
-    }
-#undef SPD_LAUNCH
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = launch_chol_lds_worklist<double>(n, A, X, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
-}
-
-const char *name_spd_tile(bool f64, int n)
-{
-    if (spd_tile2_supports(f64, n)) return name_spd_tile2(false, n);
-    if (n > spd_onewave_max(f64)) return name_tile4(f64, true, n);
-    static thread_local char buf[48];
-    snprintf(buf, sizeof buf, "matinv_spd_tile_%s<%d, %s>", f64 ? "f64" : "f32", (n + 15) / 16,
-             ((n % 16) == 0 && !(n >= 128 && !f64)) ? "true" : "false");
-    return buf;
-}
-
-const char *name_gj_tile(bool f64, int n)
-{
-    if (n > 64) return name_tile4(f64, false, n);
-    if (rowlane2_natural_use(f64, n)) return name_gj_rowlane2(f64, n);
-    if (!f64) {
-        const bool fullf = (n % 16) == 0;
-        switch ((n + 15) / 16) {
-        case 1: return fullf ? "matinv_gj_tile_f32<1, true, true>" : "matinv_gj_tile_f32<1, false, true>";
-        case 2: return fullf ? "matinv_gj_tile_f32<2, true, true>" : "matinv_gj_tile_f32<2, false, true>";
-        case 3: return fullf ? "matinv_gj_tile_f32<3, true, true>" : "matinv_gj_tile_f32<3, false, true>";
-        default: return fullf ? "matinv_gj_tile_f32<4, true, true>" : "matinv_gj_tile_f32<4, false, true>";
+    return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
+        const unsigned grid = tile_grid(batch, 8u), b = (unsigned)batch;
+        hipError_t e = hipSuccess;
+        if constexpr (sizeof(T) == 8) {
+            if (n <= 96) hipLaunchKernelGGL((matinv_gp_spd_tile_f64<6>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
+            else e = enqueue_gp_spd_tile_wide_f64(n, As, Bs, Cs, Ds, Es, out, grid, b, info, ws, stream);
+        } else {
+            if (n <= 112) hipLaunchKernelGGL((matinv_gp_spd_tile_f32<7>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
+            else if (n <= 128) hipLaunchKernelGGL((matinv_gp_spd_tile_f32<8>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
+            else e = enqueue_gp_spd_tile_wide_f32(n, As, Bs, Cs, Ds, Es, out, grid, b, info, ws, stream);
         }
-    }
-    const bool full = (n % 16) == 0;
-    switch ((n + 15) / 16) {
-    case 1: return full ? "matinv_gj_tile_f64<1, true, true>" : "matinv_gj_tile_f64<1, false, true>";
-    case 2: return full ? "matinv_gj_tile_f64<2, true, true>" : "matinv_gj_tile_f64<2, false, true>";
-    case 3: return full ? "matinv_gj_tile_f64<3, true, true>" : "matinv_gj_tile_f64<3, false, true>";
-    default: return full ? "matinv_gj_tile_f64<4, true, true>" : "matinv_gj_tile_f64<4, false, true>";
-    }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = launch_gp_lds_worklist<T>(n, As, Bs, Cs, Ds, Es, out, ws, ws + 1, info, stream);
+        return e;
+    });
 }
-
-#endif
 
 }  // namespace matinv

@@ -1,4 +1,4 @@
-// tile_screen.hpp -- the screening pass in front of the natural-order Gauss-Jordan tile kernels (tile_kernels.inc: n <= 64, one
+// tile_screen.hpp -- the screening pass in front of the natural-order Gauss-Jordan tile kernels (tile_impl.hpp: n <= 64, one
 // wavefront per matrix; tile4_impl.hpp: 64 < n <= 192 / 256, several), and the panel staging they share with it.
 #pragma once
 #include "tile_common.hpp"
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(64, 4) void matinv_gj_tile4_screen_f32(BatchRef<con
     gj_tile_screen_body<float, NT, false, false>(Ain, n_rt, batch, work_count, work_list, accept_count, accept_list, panel, lists);
 }
 
-// NATURAL_FIRST policy: run the screening kernel in front of the natural-order kernel of this size class? (tile_kernels.inc)
+// NATURAL_FIRST policy: run the screening kernel in front of the natural-order kernel of this size class? (tile_kernels.hip)
 bool tile_policy_use_screen(bool f64, int nt);
 
 }  // namespace matinv

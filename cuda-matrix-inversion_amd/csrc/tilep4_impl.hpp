@@ -393,76 +393,53 @@ __global__ __launch_bounds__(256, 3) void matinv_gj_tilep4_f32(BatchRef<const fl
     gj_tilep4_body<float, NT, FULL>(Ain, Xout, info, n_rt, batch, panel2, bball, tab, bad_count, bad_list, in_count, in_list, hint_out);
 }
 
+// wavefronts per matrix: three for 5 x 5 / 6 x 6 tiles, four beyond (matinv_gj_tilep3_* / matinv_gj_tilep4_*)
+constexpr int tilep4_waves(int nt) { return nt <= 6 ? 3 : 4; }
+
 template <class T>
 static hipError_t enqueue_tilep4(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream, int *bad_count,
                                  int *bad_list, const int *in_count, const int *in_list, hint_t *hint_out, bool expect_many = false)
 {
-    const int nt = (n + 15) / 16;
-    unsigned cap = 256u * 4u * tile_grid_rounds();
-    if (in_list && !expect_many) cap = 256u * 4u;  // usually empty: one round of resident workgroups (see enqueue_tilep)
-    const unsigned grid = (unsigned)(batch < cap ? batch : cap);
-    const unsigned b = (unsigned)batch;
-#define TP4_LAUNCH(NT_)                                                                                                \
-    if constexpr (sizeof(T) == 8) {                                                                                    \
-        if (n == 16 * NT_)                                                                                             \
-            hipLaunchKernelGGL((matinv_gj_tilep4_f64<NT_, true>), dim3(grid), dim3(256), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((matinv_gj_tilep4_f64<NT_, false>), dim3(grid), dim3(256), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-    } else {                                                                                                           \
-        if (n == 16 * NT_)                                                                                             \
-            hipLaunchKernelGGL((matinv_gj_tilep4_f32<NT_, true>), dim3(grid), dim3(256), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((matinv_gj_tilep4_f32<NT_, false>), dim3(grid), dim3(256), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-    }
-#define TP3_LAUNCH(NT_)                                                                                                \
-    if constexpr (sizeof(T) == 8) {                                                                                    \
-        if (n == 16 * NT_)                                                                                             \
-            hipLaunchKernelGGL((matinv_gj_tilep3_f64<NT_, true>), dim3(grid), dim3(192), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((matinv_gj_tilep3_f64<NT_, false>), dim3(grid), dim3(192), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-    } else {                                                                                                           \
-        if (n == 16 * NT_)                                                                                             \
-            hipLaunchKernelGGL((matinv_gj_tilep3_f32<NT_, true>), dim3(grid), dim3(192), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((matinv_gj_tilep3_f32<NT_, false>), dim3(grid), dim3(192), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out); \
-    }
-    switch (nt) {
-    case 5: TP3_LAUNCH(5) break;
-    case 6: TP3_LAUNCH(6) break;
-    case 7: TP4_LAUNCH(7) break;
-    default: TP4_LAUNCH(8) break;
-    }
-#undef TP4_LAUNCH
-#undef TP3_LAUNCH
+    // usually empty: one round of resident workgroups (see enqueue_tilep)
+    const unsigned grid = in_list && !expect_many ? tile_grid(batch, 4u, 1u) : tile_grid(batch, 4u), b = (unsigned)batch;
+    with_tile<5, 8>(tile_shape(n), [&](auto NT, auto FULL) {
+        constexpr bool F64 = sizeof(T) == 8;
+        if constexpr (tilep4_waves(NT) == 3) {
+            if constexpr (F64)
+                hipLaunchKernelGGL((matinv_gj_tilep3_f64<NT, FULL>), dim3(grid), dim3(192), 0, stream, A, X, info, n, b, bad_count, bad_list,
+                                   in_count, in_list, hint_out);
+            else
+                hipLaunchKernelGGL((matinv_gj_tilep3_f32<NT, FULL>), dim3(grid), dim3(192), 0, stream, A, X, info, n, b, bad_count, bad_list,
+                                   in_count, in_list, hint_out);
+        } else if constexpr (F64) {
+            hipLaunchKernelGGL((matinv_gj_tilep4_f64<NT, FULL>), dim3(grid), dim3(256), 0, stream, A, X, info, n, b, bad_count, bad_list,
+                               in_count, in_list, hint_out);
+        } else {
+            hipLaunchKernelGGL((matinv_gj_tilep4_f32<NT, FULL>), dim3(grid), dim3(256), 0, stream, A, X, info, n, b, bad_count, bad_list,
+                               in_count, in_list, hint_out);
+        }
+    });
     return hipGetLastError();
 }
 
 template <class T>
-static hipError_t launch_tilep4(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
+hipError_t launch_gj_tilep4(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
 {
     if (n <= 64 || n > 128) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
+    return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
+        hipError_t e = enqueue_tilep4<T>(n, A, X, batch, info, stream, ws, ws + 1, nullptr, nullptr, nullptr);
+        // singular input only: the pivoted LDS kernel reports the exact step and NaN-fills the output
+        if (e == hipSuccess) e = launch_gj_lds_worklist<T>(n, A, X, ws, ws + 1, info, stream);
         return e;
-    }
-    e = enqueue_tilep4<T>(n, A, X, batch, info, stream, ws, ws + 1, nullptr, nullptr, nullptr);
-    // singular input only: the pivoted LDS kernel reports the exact step and NaN-fills the output
-    if (e == hipSuccess) e = launch_gj_lds_worklist<T>(n, A, X, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
+    });
 }
 
 // the matrices the natural-order four-wave kernel rejected: (in_count, in_list); the singular ones among them go on to the LDS
 // kernel through (bad_count, bad_list), zeroed by the caller
 template <class T>
-static hipError_t launch_tilep4_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count,
-                                         const int *in_list, int *bad_count, int *bad_list, int *info, hipStream_t stream,
-                                         hint_t *hint_out, bool expect_many = false)
+hipError_t launch_gj_tilep4_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count, const int *in_list,
+                                     int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many)
 {
     hipError_t e = enqueue_tilep4<T>(n, A, X, batch, info, stream, bad_count, bad_list, in_count, in_list, hint_out, expect_many);
     if (e == hipSuccess) e = launch_gj_lds_worklist<T>(n, A, X, bad_count, bad_list, info, stream);

@@ -9,25 +9,15 @@
 
 namespace matinv {
 
-template <>
-hipError_t launch_gj_tilep4<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, int *info, hipStream_t stream)
-{
-    return launch_tilep4<double>(n, A, X, batch, info, stream);
-}
-
-template <>
-hipError_t launch_gj_tilep4_worklist<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, const int *in_count,
-                                            const int *in_list, int *bad_count, int *bad_list, int *info, hipStream_t stream,
-                                            hint_t *hint_out, bool expect_many)
-{
-    return launch_tilep4_worklist<double>(n, A, X, batch, in_count, in_list, bad_count, bad_list, info, stream, hint_out, expect_many);
-}
+template hipError_t launch_gj_tilep4<double>(int, BatchRef<const double>, BatchRef<double>, size_t, int *, hipStream_t);
+template hipError_t launch_gj_tilep4_worklist<double>(int, BatchRef<const double>, BatchRef<double>, size_t, const int *, const int *, int *,
+                                                      int *, int *, hipStream_t, hint_t *, bool);
 
 const char *name_gj_tilep4(bool f64, int n)
 {
+    const TileShape s = tile_shape(n);
     static thread_local char buf[48];
-    const int nt = (n + 15) / 16;
-    snprintf(buf, sizeof buf, "matinv_gj_tilep%d_%s<%d, %s>", nt <= 6 ? 3 : 4, f64 ? "f64" : "f32", nt, (n % 16) == 0 ? "true" : "false");
+    snprintf(buf, sizeof buf, "matinv_gj_tilep%d_%s<%d, %s>", tilep4_waves(s.nt), f64 ? "f64" : "f32", s.nt, s.full ? "true" : "false");
     return buf;
 }
 

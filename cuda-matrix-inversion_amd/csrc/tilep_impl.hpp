@@ -1,8 +1,8 @@
 // tilep_impl.hpp (instantiated by tilep_kernels.hip for f64 and tilep_f32_kernels.hip for f32) -- kernel family "TILEP":
-// the MFMA accumulator-tile Gauss-Jordan of tile_kernels.inc (read that header first) with TRUE PARTIAL PIVOTING inside
+// the MFMA accumulator-tile Gauss-Jordan of tile_impl.hpp (read that header first) with TRUE PARTIAL PIVOTING inside
 // the kernel, for GENERAL matrices, n <= 64, one matrix per wavefront.
 //
-// What pivoting changes. tile_kernels.inc eliminates in natural order: the four pivot rows of block kb are the rows that
+// What pivoting changes. tile_impl.hpp eliminates in natural order: the four pivot rows of block kb are the rows that
 // ONE accumulator register (tile row kb/4, register kb%4) holds across the four lane groups, which makes the B operand
 // of the rank-4 update free. With a pivot search the four pivot rows of a block are wherever the search finds them:
 //   * rows never move (IMPLICIT pivoting): every row keeps its register slot for the whole elimination and the row /
@@ -212,7 +212,7 @@ __device__ __forceinline__ void gj_tilep_body(BatchRef<const T> Ain, BatchRef<T>
         T aop[NT], bop[NT];  // operands of the block step whose MFMAs are still owed
 
         // One pipeline turn = everything block nb = (tile column tKn [compile time], block rKn inside it [run time]) needs
-        // before its MFMAs, interleaved with the MFMAs of the PREVIOUS block (look-ahead, as in tile_kernels.inc):
+        // before its MFMAs, interleaved with the MFMAs of the PREVIOUS block (look-ahead, as in tile_impl.hpp):
         //   1. previous block's update of tile column tKn (it holds the pivot columns of block nb)
         //   2. the four pivot columns -> LDS; one row per lane back
         //   3. pivot search + in-place Gauss-Jordan of the n x 4 panel, 12 stages, the other NT (NT-1) MFMAs of the
@@ -454,61 +454,38 @@ template <class T>
 static hipError_t enqueue_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream,
                                 const int *in_count, const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list, bool expect_many = false)
 {
-    const int nt = (n + 15) / 16;
-    unsigned cap = 256u * 12u * tile_grid_rounds();
     // work-list form: the list is usually empty -- one round of resident workgroups that stride over it. Behind the screening pass
     // (expect_many) most of the batch is on it: one workgroup per matrix as in the direct form (a workgroup beyond the list's
     // length reads the count and leaves), otherwise 30 matrices per wave, each behind a dependent load of its index
-    if (in_list && !expect_many) cap = 256u * 12u;
-    const unsigned grid = (unsigned)(batch < cap ? batch : cap);
-    const unsigned b = (unsigned)batch;
-#define TP_LAUNCH(NT_)                                                                                                 \
-    if constexpr (sizeof(T) == 8) {                                                                                    \
-        if (n == 16 * NT_)                                                                                             \
-            hipLaunchKernelGGL((matinv_gj_tilep_f64<NT_, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out, bad_count, bad_list); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((matinv_gj_tilep_f64<NT_, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out, bad_count, bad_list); \
-    } else {                                                                                                           \
-        if (n == 16 * NT_)                                                                                             \
-            hipLaunchKernelGGL((matinv_gj_tilep_f32<NT_, true>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out, bad_count, bad_list); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((matinv_gj_tilep_f32<NT_, false>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out, bad_count, bad_list); \
-    }
-    switch (nt) {
-    case 1: TP_LAUNCH(1) break;
-    case 2: TP_LAUNCH(2) break;
-    case 3: TP_LAUNCH(3) break;
-    default: TP_LAUNCH(4) break;
-    }
-#undef TP_LAUNCH
+    const unsigned grid = in_list && !expect_many ? tile_grid(batch, 12u, 1u) : tile_grid(batch, 12u), b = (unsigned)batch;
+    with_tile<1, 4>(tile_shape(n), [&](auto NT, auto FULL) {
+        if constexpr (sizeof(T) == 8)
+            hipLaunchKernelGGL((matinv_gj_tilep_f64<NT, FULL>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out,
+                               bad_count, bad_list);
+        else
+            hipLaunchKernelGGL((matinv_gj_tilep_f32<NT, FULL>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out,
+                               bad_count, bad_list);
+    });
     return hipGetLastError();
 }
 
 template <class T>
-static hipError_t launch_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
+hipError_t launch_gj_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
 {
     if (n < 1 || n > 64) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    int *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (batch + 1) * sizeof(int), stream);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(ws, 0, sizeof(int), stream);
-    if (e != hipSuccess) {
-        (void)scratch_free(ws, stream);
+    return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
+        hipError_t e = enqueue_tilep<T>(n, A, X, batch, info, stream, nullptr, nullptr, nullptr, ws, ws + 1);
+        if (e == hipSuccess) e = launch_gj_row_worklist<T>(n, A, X, ws, ws + 1, info, stream);
         return e;
-    }
-    e = enqueue_tilep<T>(n, A, X, batch, info, stream, nullptr, nullptr, nullptr, ws, ws + 1);
-    if (e == hipSuccess) e = launch_gj_row_worklist<T>(n, A, X, ws, ws + 1, info, stream);
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
+    });
 }
 
 // the matrices the natural-order kernel rejected: (in_count, in_list) in device memory; the singular ones among them go on
 // to the ROW kernel through (bad_count, bad_list), which the caller has zeroed
 template <class T>
-static hipError_t launch_tilep_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count,
-                                        const int *in_list, int *bad_count, int *bad_list, int *info, hipStream_t stream,
-                                        hint_t *hint_out, bool expect_many = false)
+hipError_t launch_gj_tilep_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count, const int *in_list,
+                                    int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many)
 {
     hipError_t e = enqueue_tilep<T>(n, A, X, batch, info, stream, in_count, in_list, hint_out, bad_count, bad_list, expect_many);
     if (e == hipSuccess) e = launch_gj_row_worklist<T>(n, A, X, bad_count, bad_list, info, stream);

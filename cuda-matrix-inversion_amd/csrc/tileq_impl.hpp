@@ -9,7 +9,7 @@
 // of a block step at 128 x 128) and, with the search repeated by every wave, 48 k vector instructions per 128 x 128 matrix.
 //
 // This family turns the step around. The four pivot ROWS of block kb are fixed: the rows that accumulator register kb % 4
-// of tile row kb / 4 holds across the four lane groups -- the rows the natural-order kernel uses (tile_kernels.inc), so
+// of tile row kb / 4 holds across the four lane groups -- the rows the natural-order kernel uses (tile_impl.hpp), so
 // staging them is ONE LDS store per tile column and perfectly balanced over the waves. The search runs ALONG those rows,
 // over the columns not used yet: with W = A^T this is exactly the oracle's row pivoting on A (column k of A, rows not
 // used yet; /root/reference/src/gauss/inverse_gpu.cu:24-33 = cublasSgetrfBatched, the LAPACK rule). What is found at run
@@ -495,53 +495,30 @@ MATINV_TILEQ_KERNEL(matinv_gj_tileqw_f32, float, 64 * NT, 1, NT, 1)
 
 constexpr int tileq_limit(bool f64) { return f64 ? 192 : 256; }
 
-template <class T>
-static hipError_t enqueue_tileq(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream, int *bad_count,
-                                int *bad_list, const int *in_count, const int *in_list, hint_t *hint_out)
-{
-    const int nt = (n + 15) / 16;
-    const unsigned per_cu = 1u;  // the matrix fills most of the CU's register file
-    unsigned cap = 256u * per_cu * tile_grid_rounds();
-    if (in_list) cap = 256u * per_cu;  // usually empty: one round of resident workgroups
-    const unsigned grid = (unsigned)(batch < cap ? batch : cap);
-    const unsigned b = (unsigned)batch;
-// (run-time n only: at these sizes the kernel is far from memory-bound, the compile-time-n twins bought nothing measurable and doubled
-// the build time of this family)
-#define TQ_LAUNCH(KERN, NT_, THREADS)                                                                                  \
-    hipLaunchKernelGGL((KERN<NT_, false>), dim3(grid), dim3(THREADS), 0, stream, A, X, info, n, b, bad_count, bad_list, in_count, in_list, hint_out);
-#define TQ_CASEW(NT_)                                                                                                  \
-    case NT_:                                                                                                          \
-        if constexpr (sizeof(T) == 8) {                                                                                \
-            if constexpr (NT_ <= 12) { TQ_LAUNCH(matinv_gj_tileqw_f64, NT_, 64 * NT_) }                                \
-        } else { TQ_LAUNCH(matinv_gj_tileqw_f32, NT_, 64 * NT_) }                                                      \
-        break;
-    switch (nt) {
-        TQ_CASEW(9)
-        TQ_CASEW(10)
-        TQ_CASEW(11)
-        TQ_CASEW(12)
-        TQ_CASEW(13)
-        TQ_CASEW(14)
-        TQ_CASEW(15)
-        TQ_CASEW(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef TQ_CASEW
-#undef TQ_LAUNCH
-    return hipGetLastError();
-}
-
 // Direct form (in_list == nullptr): the whole batch. Work-list form: the matrices the natural-order kernel of this size rejected,
 // (in_count, in_list) in device memory. No kernel behind this one serves every 128 < n <= 256, so a singular matrix is finished
 // here: info = first column of A without a usable pivot + 1 (the oracle's code), NaN-filled output. (bad_count / bad_list: the hand-over
 // to the pivoted LDS kernel that the n <= 128 instantiations of tools/tileq_stamps.hip can use; nullptr here.)
 template <class T>
-static hipError_t launch_tileq(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream, const int *in_count,
-                               const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list)
+hipError_t launch_gj_tileq(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream, const int *in_count,
+                           const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list)
 {
     if (n <= 128 || n > tileq_limit(sizeof(T) == 8)) return hipErrorInvalidValue;
-    if (batch == 0) return hipSuccess;
-    return enqueue_tileq<T>(n, A, X, batch, info, stream, bad_count, bad_list, in_count, in_list, hint_out);
+    if (batch == 0) return in_count ? debug_note_rejects(in_count, stream) : hipSuccess;
+    // the matrix fills most of the CU's register file: one workgroup per CU; the work list is usually empty: one round of them
+    const unsigned grid = in_list ? tile_grid(batch, 1u, 1u) : tile_grid(batch, 1u), b = (unsigned)batch;
+    // (run-time n only: at these sizes the kernel is far from memory-bound, the compile-time-n twins bought nothing measurable and doubled
+    // the build time of this family)
+    with_nt<9, 16>((n + 15) / 16, [&](auto NT) {
+        if constexpr (sizeof(T) == 4)
+            hipLaunchKernelGGL((matinv_gj_tileqw_f32<NT, false>), dim3(grid), dim3(64 * NT), 0, stream, A, X, info, n, b, bad_count, bad_list,
+                               in_count, in_list, hint_out);
+        else if constexpr (NT <= 12)
+            hipLaunchKernelGGL((matinv_gj_tileqw_f64<NT, false>), dim3(grid), dim3(64 * NT), 0, stream, A, X, info, n, b, bad_count, bad_list,
+                               in_count, in_list, hint_out);
+    });
+    hipError_t e = hipGetLastError();
+    return (e != hipSuccess || !in_count) ? e : debug_note_rejects(in_count, stream);
 }
 
 }  // namespace matinv

@@ -6,13 +6,8 @@ namespace matinv {
 
 bool tileq_supports(bool f64, int n) { return n > 128 && n <= tileq_limit(f64); }
 
-template <>
-hipError_t launch_gj_tileq<double>(int n, BatchRef<const double> A, BatchRef<double> X, size_t batch, int *info, hipStream_t stream,
-                                   const int *in_count, const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list)
-{
-    hipError_t e = launch_tileq<double>(n, A, X, batch, info, stream, in_count, in_list, hint_out, bad_count, bad_list);
-    return (e != hipSuccess || !in_count) ? e : debug_note_rejects(in_count, stream);
-}
+template hipError_t launch_gj_tileq<double>(int, BatchRef<const double>, BatchRef<double>, size_t, int *, hipStream_t, const int *, const int *,
+                                          hint_t *, int *, int *);
 
 const char *name_gj_tileq(bool f64, int n)
 {

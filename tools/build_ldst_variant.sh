@@ -1,5 +1,5 @@
 #!/bin/bash
-# Profiling only: libmatinv_hip_ldst.so = the library with the natural-order tile kernels (tile_kernels.inc, the fp64 translation unit
+# Profiling only: libmatinv_hip_ldst.so = the library with the natural-order tile kernels (tile_impl.hpp, the fp64 translation unit
 # tile_gj_kernels.hip) reduced to their loads and stores (-DMATINV_TILE_LDST_ONLY: same access pattern, same launch shape, no
 # elimination). Used through MATINV_LIB to price the memory side of the headline kernel by itself (tools/profile_round.sh,
 # tools/clock_power.sh). Run here (hipcc cross-compiles); the .so travels.
