@@ -39,6 +39,8 @@ NATIVE_NAMES = [
     "matinv_set_gj_policy", "matinv_device_count", "matinv_shard_range", "matinv_inverse_batched_host_multi", "matinv_comm_unique_id",
     "matinv_comm_init_rank", "matinv_comm_destroy", "matinv_allgather_shards", "matinv_allgather_local", "matinv_allgather_local_after", "matinv_debug_rejects",
     "matinv_solve_batched", "matinv_solve_batched_ex", "matinv_solve_kernel_name", "matinv_solve_batched_host",
+    "matinv_logdet_batched", "matinv_logdet_batched_ex", "matinv_logdet_kernel_name", "matinv_logdet_batched_host",
+    "matinv_logml_batched", "matinv_logml_batched_host",
 ]
 GJ_NATURAL_FIRST, GJ_PIVOT, GJ_ADAPTIVE = 0, 1, 2
 
@@ -82,6 +84,18 @@ def lib() -> ctypes.CDLL:
     L.matinv_solve_kernel_name.argtypes = [ci, ci, ci, ci, ci]
     L.matinv_solve_batched_host.restype = ci
     L.matinv_solve_batched_host.argtypes = [ci, ci, ci, ci, vp, vp, vp, sz, vp]
+    L.matinv_logdet_batched.restype = ci
+    L.matinv_logdet_batched.argtypes = [ci, ci, ci, vp, sz, vp, vp, sz, vp, vp]
+    L.matinv_logdet_batched_ex.restype = ci
+    L.matinv_logdet_batched_ex.argtypes = [ci, ci, ci, vp, sz, vp, vp, sz, vp, vp, ci]
+    L.matinv_logdet_kernel_name.restype = ctypes.c_char_p
+    L.matinv_logdet_kernel_name.argtypes = [ci, ci, ci, ci]
+    L.matinv_logdet_batched_host.restype = ci
+    L.matinv_logdet_batched_host.argtypes = [ci, ci, ci, vp, vp, vp, sz, vp]
+    L.matinv_logml_batched.restype = ci
+    L.matinv_logml_batched.argtypes = [ci, ci, vp, vp, vp, vp, sz, vp, vp]
+    L.matinv_logml_batched_host.restype = ci
+    L.matinv_logml_batched_host.argtypes = [ci, ci, vp, vp, vp, vp, sz, vp]
     L.matinv_select_kernel.restype = ci
     L.matinv_select_kernel.argtypes = [ci, ci, ci]
     L.matinv_kernel_name.restype = ctypes.c_char_p

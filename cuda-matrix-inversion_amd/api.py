@@ -267,6 +267,99 @@ def solve_kernel_name(algo: int, dtype, n: int, nrhs: int, kernel: int = KERNEL_
     return _lib.lib().matinv_solve_kernel_name(algo, code, n, nrhs, kernel).decode()
 
 
+def logdet_batched(A, n: int, algo: int = ALGO_GAUSS_JORDAN, sign=None, out=None, info=None, kernel: int = KERNEL_AUTO,
+                   batch: int | None = None, stride: int | None = None):
+    """sign_k * exp(logabsdet_k) = det A_k on device tensors, torch's current stream, no copies (matinv_logdet_batched_ex; asynchronous).
+
+    A: `batch` n x n matrices, column-major, matrix k at element k*stride (default n*n). ALGO_CHOLESKY reads the lower triangle only
+    (SPD input, sign +1); ALGO_GAUSS_JORDAN serves general matrices. sign, out: optional result tensors of A's dtype with at least
+    `batch` elements (allocated when None; elements beyond `batch` are left alone). info: optional int32[batch].
+    Returns (sign, logabsdet).
+    """
+    import torch
+    _require_cuda(A, sign, out, info)
+    stride = n * n if stride is None else int(stride)
+    if batch is None:
+        batch = A.numel() // stride
+    if out is None:
+        out = torch.empty(batch, dtype=A.dtype, device=A.device)
+    if sign is None:
+        sign = torch.empty(batch, dtype=A.dtype, device=A.device)
+    if out.dtype != A.dtype or sign.dtype != A.dtype:
+        raise TypeError("sign and out must have the dtype of A")
+    if out.numel() < batch or sign.numel() < batch:
+        raise ValueError("sign and out need at least `batch` elements")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batch):
+        raise ValueError("info must be an int32 tensor with at least `batch` elements")
+    with torch.cuda.device(A.device):
+        _lib.check(_lib.lib().matinv_logdet_batched_ex(
+            algo, _torch_dtype_code(A), n, ctypes.c_void_p(A.data_ptr()), stride, ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(sign.data_ptr()), batch, ctypes.c_void_p(info.data_ptr()) if info is not None else None,
+            _stream_ptr(A), kernel))
+    return sign, out
+
+
+def logdet_batched_host(As: np.ndarray, n: int, algo: int = ALGO_GAUSS_JORDAN):
+    """matinv_logdet_batched_host on a numpy batch (packed, column-major): returns (sign, logabsdet, info). Synchronous."""
+    As = np.ascontiguousarray(As)
+    batch = As.size // (n * n)
+    sign = np.empty(batch, dtype=As.dtype)
+    out = np.empty(batch, dtype=As.dtype)
+    info = np.zeros(batch, dtype=np.int32)
+    _lib.check(_lib.lib().matinv_logdet_batched_host(
+        algo, _np_dtype_code(As.dtype), n, As.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
+        sign.ctypes.data_as(ctypes.c_void_p), batch, info.ctypes.data_as(ctypes.c_void_p)))
+    return sign, out, info
+
+
+def logml_batched(n, Bs, Cs, Ds, out=None, batchSize=None, info=None):
+    """logml[k] = -1/2 d_k^T M_k^-1 d_k - 1/2 log det M_k - n/2 log(2 pi), M_k = B_k + diag c_k, on device tensors
+    (matinv_logml_batched; asynchronous on torch's current stream). Cs may be None (M = B). Only B's lower triangle is read and
+    no input is modified. Returns out."""
+    import torch
+    _require_cuda(Bs, Cs, Ds, out, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    if out is None:
+        out = torch.empty(batchSize, dtype=Bs.dtype, device=Bs.device)
+    if Ds.dtype != Bs.dtype or out.dtype != Bs.dtype or (Cs is not None and Cs.dtype != Bs.dtype):
+        raise TypeError("Bs, Cs, Ds and out must have one dtype")
+    if Ds.numel() < batchSize * n or out.numel() < batchSize or (Cs is not None and Cs.numel() < batchSize * n):
+        raise ValueError("Cs and Ds need batchSize*n elements, out batchSize")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_logml_batched(
+            _torch_dtype_code(Bs), n, ctypes.c_void_p(Bs.data_ptr()), ctypes.c_void_p(Cs.data_ptr()) if Cs is not None else None,
+            ctypes.c_void_p(Ds.data_ptr()), ctypes.c_void_p(out.data_ptr()), batchSize,
+            ctypes.c_void_p(info.data_ptr()) if info is not None else None, _stream_ptr(Bs)))
+    return out
+
+
+def logml_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray):
+    """matinv_logml_batched_host on numpy batches (packed; Cs may be None): returns (logml, info). Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Ds = np.ascontiguousarray(Ds)
+    Cs = None if Cs is None else np.ascontiguousarray(Cs)
+    if Ds.dtype != Bs.dtype or (Cs is not None and Cs.dtype != Bs.dtype):
+        raise TypeError("Bs, Cs and Ds must have one dtype")
+    batch = Bs.size // (n * n)
+    if Ds.size < batch * n or (Cs is not None and Cs.size < batch * n):
+        raise ValueError("Cs and Ds smaller than batch*n")
+    out = np.empty(batch, dtype=Bs.dtype)
+    info = np.zeros(batch, dtype=np.int32)
+    _lib.check(_lib.lib().matinv_logml_batched_host(
+        _np_dtype_code(Bs.dtype), n, Bs.ctypes.data_as(ctypes.c_void_p), Cs.ctypes.data_as(ctypes.c_void_p) if Cs is not None else None,
+        Ds.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), batch, info.ctypes.data_as(ctypes.c_void_p)))
+    return out, info
+
+
+def logdet_kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> str:
+    """matinv_logdet_kernel_name: the kernel a logdet request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_logdet_kernel_name(algo, code, n, kernel).decode()
+
+
 mean_batched = calcluateMean
 variance_batched = calcluateVariance
 

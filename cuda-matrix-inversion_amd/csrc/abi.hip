@@ -756,6 +756,153 @@ int gp_host(int n, const void *hA, const void *hB, const void *hC, const void *h
     return MATINV_OK;
 }
 
+// ---- batched log-determinant and GP log marginal likelihood (matinv_logdet_batched, matinv_logml_batched) --------------------------
+// Which kernel a logdet request takes: the MFMA tile sweep (Cholesky, n <= 96), the pivoting row kernel (Gauss-Jordan, n <= 64),
+// the global-memory kernel for everything else up to n = 1024.
+enum { LOGDET_TILE = 0, LOGDET_ROW = 1, LOGDET_GLOBAL = 2 };
+int logdet_route(int algo, int n, int kernel)
+{
+    const bool tile = algo == MATINV_ALGO_CHOLESKY && logdet_tile_supports(n);
+    const bool row = algo == MATINV_ALGO_GAUSS_JORDAN && logdet_row_supports(n);
+    switch (kernel) {
+    case MATINV_KERNEL_AUTO: return tile ? LOGDET_TILE : row ? LOGDET_ROW : LOGDET_GLOBAL;
+    case MATINV_KERNEL_TILE:
+        if (!tile) return fail(MATINV_ERR_UNSUPPORTED, "the logdet tile kernel serves MATINV_ALGO_CHOLESKY with n <= 96 only (n=%d)", n);
+        return LOGDET_TILE;
+    case MATINV_KERNEL_ROW:
+        if (!row) return fail(MATINV_ERR_UNSUPPORTED, "the logdet row kernel serves MATINV_ALGO_GAUSS_JORDAN with n <= 64 only (n=%d)", n);
+        return LOGDET_ROW;
+    case MATINV_KERNEL_GLOBAL: return LOGDET_GLOBAL;
+    default: return fail(MATINV_ERR_UNSUPPORTED, "kernel family %d has no logdet kernel (TILE, ROW, GLOBAL)", kernel);
+    }
+}
+
+int logdet_check_args(int algo, int dtype, int n, const void *dA, size_t strideA, const void *dLogAbsDet, size_t batch, int kernel)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (algo != MATINV_ALGO_GAUSS_JORDAN && algo != MATINV_ALGO_CHOLESKY) return fail(MATINV_ERR_ARG, "unknown algorithm %d", algo);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (kernel < MATINV_KERNEL_AUTO || kernel > MATINV_KERNEL_TILEP) return fail(MATINV_ERR_ARG, "unknown kernel family %d", kernel);
+    if (batch == 0) return MATINV_OK;
+    if (!dA || !dLogAbsDet) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (batch > 1 && strideA < (size_t)n * n) return fail(MATINV_ERR_ARG, "stride too small (strideA >= n*n)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    return MATINV_OK;
+}
+
+template <class T>
+int logdet_strided(int algo, int n, const void *dA, size_t strideA, void *dLogAbsDet, void *dSign, size_t batch, int *dInfo,
+                   hipStream_t stream, int kernel)
+{
+    const int route = logdet_route(algo, n, kernel);
+    if (route < 0) return route;
+    int rc = check_device();
+    if (rc) return rc;
+    const T *A = static_cast<const T *>(dA);
+    T *ld = static_cast<T *>(dLogAbsDet), *sg = static_cast<T *>(dSign);
+    hipError_t e;
+    if (route == LOGDET_TILE) e = launch_logdet_tile<T>(n, false, A, strideA, nullptr, nullptr, ld, sg, batch, dInfo, stream);
+    else if (route == LOGDET_ROW) e = launch_logdet_row<T>(n, A, strideA, ld, sg, batch, dInfo, stream);
+    else e = launch_logdet_global<T>(n, algo == MATINV_ALGO_CHOLESKY, A, strideA, nullptr, ld, sg, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "logdet launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int logdet_host(int algo, int n, const void *hA, void *hLogAbsDet, void *hSign, size_t batch, int *info)
+{
+    const size_t ea = (size_t)n * n * batch;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dA = nullptr, *dOut = nullptr;  // dOut: logabsdet, then sign
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dA), ea * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dOut), 2 * batch * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dA, hA, ea * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        rc = logdet_strided<T>(algo, n, dA, (size_t)n * n, dOut, hSign ? dOut + batch : nullptr, batch, dInfo, nullptr, MATINV_KERNEL_AUTO);
+    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hLogAbsDet, dOut, batch * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hSign) e = hipMemcpy(hSign, dOut + batch, batch * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dA);
+    staging_free(dOut);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "logdet host<->device");
+    return MATINV_OK;
+}
+
+int logml_check_args(int dtype, int n, const void *dBs, const void *dDs, const void *dLogml, size_t batch)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (!dBs || !dDs || !dLogml) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    return MATINV_OK;
+}
+
+// n <= 96: the bordered tile kernel. Beyond: the variance pipeline with a = d and e = 0 puts -d^T M^-1 d into scratch, the global
+// logdet kernel with diag = c the determinant (and info), a small kernel combines them.
+template <class T>
+int logml_dispatch(int n, const void *dBs, const void *dCs, const void *dDs, void *dLogml, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *d = static_cast<const T *>(dDs);
+    T *out = static_cast<T *>(dLogml);
+    if (logdet_tile_supports(n)) {
+        const hipError_t e = launch_logdet_tile<T>(n, true, B, (size_t)n * n, c, d, out, nullptr, batch, dInfo, stream);
+        if (e != hipSuccess) return fail_hip(e, "logml launch");
+        return MATINV_OK;
+    }
+    // scratch: [e = 0 | (c = 0 when absent)] [var] [logdet]
+    const size_t zeros = batch + (c ? 0 : batch * (size_t)n);
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), (zeros + 2 * batch) * sizeof(T), stream);
+    if (e != hipSuccess) return fail_hip(e, "logml workspace");
+    T *zero_e = ws, *var = ws + zeros, *ld = var + batch;
+    const T *cc = c ? c : ws + batch;
+    e = hipMemsetAsync(ws, 0, zeros * sizeof(T), stream);
+    if (e == hipSuccess) rc = gp_dispatch<T>(n, d, B, cc, nullptr, zero_e, var, batch, nullptr, stream, true);
+    if (e == hipSuccess && rc == MATINV_OK) e = launch_logdet_global<T>(n, true, B, (size_t)n * n, c, ld, nullptr, batch, dInfo, stream);
+    if (e == hipSuccess && rc == MATINV_OK) e = launch_logml_combine<T>(n, var, ld, out, batch, stream);
+    const hipError_t e2 = scratch_free(ws, stream);
+    if (rc != MATINV_OK) return rc;
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail_hip(e, "logml launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int logml_host(int n, const void *hBs, const void *hCs, const void *hDs, void *hLogml, size_t batch, int *info)
+{
+    const size_t vec = (size_t)n * batch, mat = vec * n;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dOut = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dOut), batch * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = logml_dispatch<T>(n, dB, dC, dD, dOut, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hLogml, dOut, batch * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dOut);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "logml host<->device");
+    return MATINV_OK;
+}
+
 template <class T>
 int lu_kernel(int n)
 {
@@ -965,6 +1112,59 @@ int matinv_solve_batched_host(int algo, int dtype, int n, int nrhs, const void *
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return solve_host<double>(algo, n, nrhs, hA, hB, hX, batch, info);
     return solve_host<float>(algo, n, nrhs, hA, hB, hX, batch, info);
+}
+
+int matinv_logdet_batched_ex(int algo, int dtype, int n, const void *dA, size_t strideA, void *dLogAbsDet, void *dSign, size_t batch,
+                             int *dInfo, void *stream, int kernel)
+{
+    int rc = logdet_check_args(algo, dtype, n, dA, strideA, dLogAbsDet, batch, kernel);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return logdet_strided<double>(algo, n, dA, strideA, dLogAbsDet, dSign, batch, dInfo, st, kernel);
+    return logdet_strided<float>(algo, n, dA, strideA, dLogAbsDet, dSign, batch, dInfo, st, kernel);
+}
+
+int matinv_logdet_batched(int algo, int dtype, int n, const void *dA, size_t strideA, void *dLogAbsDet, void *dSign, size_t batch,
+                          int *dInfo, void *stream)
+{
+    return matinv_logdet_batched_ex(algo, dtype, n, dA, strideA, dLogAbsDet, dSign, batch, dInfo, stream, MATINV_KERNEL_AUTO);
+}
+
+const char *matinv_logdet_kernel_name(int algo, int dtype, int n, int kernel)
+{
+    if (logdet_check_args(algo, dtype, n, nullptr, 0, nullptr, 0, kernel) != MATINV_OK || n > 1024) return "";
+    const int route = logdet_route(algo, n, kernel);
+    const bool f64 = dtype == MATINV_F64;
+    if (route == LOGDET_TILE) return name_logdet_tile(f64, false, n);
+    if (route == LOGDET_ROW) return name_logdet_row(f64, n);
+    if (route == LOGDET_GLOBAL) return name_logdet_global(f64, algo == MATINV_ALGO_CHOLESKY);
+    return "";
+}
+
+int matinv_logdet_batched_host(int algo, int dtype, int n, const void *hA, void *hLogAbsDet, void *hSign, size_t batch, int *info)
+{
+    int rc = logdet_check_args(algo, dtype, n, hA, (size_t)n * n, hLogAbsDet, batch, MATINV_KERNEL_AUTO);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return logdet_host<double>(algo, n, hA, hLogAbsDet, hSign, batch, info);
+    return logdet_host<float>(algo, n, hA, hLogAbsDet, hSign, batch, info);
+}
+
+int matinv_logml_batched(int dtype, int n, const void *dBs, const void *dCs, const void *dDs, void *dLogml, size_t batch, int *dInfo,
+                         void *stream)
+{
+    int rc = logml_check_args(dtype, n, dBs, dDs, dLogml, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return logml_dispatch<double>(n, dBs, dCs, dDs, dLogml, batch, dInfo, st);
+    return logml_dispatch<float>(n, dBs, dCs, dDs, dLogml, batch, dInfo, st);
+}
+
+int matinv_logml_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hLogml, size_t batch, int *info)
+{
+    int rc = logml_check_args(dtype, n, hBs, hDs, hLogml, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return logml_host<double>(n, hBs, hCs, hDs, hLogml, batch, info);
+    return logml_host<float>(n, hBs, hCs, hDs, hLogml, batch, info);
 }
 
 int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dDs,

@@ -322,6 +322,28 @@ template <class T>
 hipError_t launch_solve_gemm(int n, int nrhs, const T *Ainv, BatchRef<const T> B, BatchRef<T> X, size_t count, hipStream_t stream);
 const char *name_solve_gemm(bool f64);
 
+// Batched log-determinant and GP log marginal likelihood (matinv_logdet_batched, matinv_logml_batched).
+// (a) symmetric MFMA tile sweep, one wavefront per matrix, n <= 96 (logdet_tile_kernels.hip, logdet_tile_f32_kernels.hip). border == false:
+//     out0 = log det A (SPD, lower triangle), out1 = sign (optional); border == true: out0 = logml of B + diag Cs (Cs optional) and Ds
+bool logdet_tile_supports(int n);
+template <class T>
+hipError_t launch_logdet_tile(int n, bool border, const T *As, size_t stride, const T *Cs, const T *Ds, T *out0, T *out1, size_t batch,
+                              int *info, hipStream_t stream);
+const char *name_logdet_tile(bool f64, bool border, int n);
+// (b) pivoting row kernel for general matrices, n <= 64 (logdet_row_kernels.hip)
+bool logdet_row_supports(int n);
+template <class T>
+hipError_t launch_logdet_row(int n, const T *As, size_t stride, T *logabs, T *sign, size_t batch, int *info, hipStream_t stream);
+const char *name_logdet_row(bool f64, int n);
+// (c) the functional path, n <= 1024 (logdet_global_kernels.hip): LU with partial pivoting, or (spd) L D L^T of A + diag(diag)
+bool logdet_global_supports(int n);
+template <class T>
+hipError_t launch_logdet_global(int n, bool spd, const T *As, size_t stride, const T *diag, T *logabs, T *sign, size_t batch, int *info,
+                                hipStream_t stream);
+const char *name_logdet_global(bool f64, bool spd);
+template <class T>
+hipError_t launch_logml_combine(int n, const T *var, const T *logdet, T *logml, size_t batch, hipStream_t stream);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 const char *name_gp_lds(bool f64);

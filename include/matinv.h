@@ -151,6 +151,44 @@ int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, cons
 int matinv_variance_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dEs,
                             void *dVars, size_t batch, int *dInfo, void *stream);
 
+/* Batched log-determinant: sign_k * exp(logabsdet_k) = det A_k, without ever forming the determinant (it may overflow or underflow
+ * the number format; log|det| does not).
+ *   dA          in : n x n, column-major, matrix k at dA + k*strideA (strideA >= n*n). Never written. MATINV_ALGO_CHOLESKY reads only
+ *                    the lower triangle (SPD input; sign is +1), MATINV_ALGO_GAUSS_JORDAN serves general matrices with partial
+ *                    pivoting (the sign includes the parity of the row exchanges).
+ *   dLogAbsDet  out: batch scalars of A's dtype.
+ *   dSign       out: optional (NULL allowed) batch scalars of A's dtype: +1 or -1.
+ *   dInfo       out: optional int[batch] (device), the codes of matinv_inverse_batched (k+1: no usable pivot at step k / leading minor
+ *                    k+1 not positive). For info != 0 both outputs of that matrix are NaN.
+ *   stream         : hipStream_t as void*. Asynchronous; no host synchronisation.
+ * Paths: Cholesky, n <= 96: one MFMA tile kernel (the factorisation half of the symmetric blocked sweep, pivots folded into a
+ * mantissa / exponent pair). Gauss-Jordan, n <= 64: one matrix per wavefront, row per lane, partial pivoting. Everything else up to
+ * n = 1024: one workgroup per matrix on a working copy in library scratch (k-range chunks under the blocked-path workspace cap).
+ * The result for matrix k depends on matrix k alone. batch == 0 is a no-op; bad arguments return MATINV_ERR_ARG without touching a
+ * device; n > 1024: MATINV_ERR_UNSUPPORTED. */
+int matinv_logdet_batched(int algo, int dtype, int n, const void *dA, size_t strideA, void *dLogAbsDet, void *dSign, size_t batch,
+                          int *dInfo, void *stream);
+/* Same, forcing a kernel: MATINV_KERNEL_AUTO = as above; MATINV_KERNEL_TILE (Cholesky, n <= 96), MATINV_KERNEL_ROW (Gauss-Jordan,
+ * n <= 64), MATINV_KERNEL_GLOBAL (both, n <= 1024) force that kernel and return MATINV_ERR_UNSUPPORTED outside its range; any other
+ * family: MATINV_ERR_UNSUPPORTED; an unknown value: MATINV_ERR_ARG. */
+int matinv_logdet_batched_ex(int algo, int dtype, int n, const void *dA, size_t strideA, void *dLogAbsDet, void *dSign, size_t batch,
+                             int *dInfo, void *stream, int kernel);
+/* Name of the __global__ function a logdet request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_logdet_kernel_name(int algo, int dtype, int n, int kernel);
+/* Host-pointer form (packed: stride n*n; hSign and `info` optional). Synchronous. */
+int matinv_logdet_batched_host(int algo, int dtype, int n, const void *hA, void *hLogAbsDet, void *hSign, size_t batch, int *info);
+
+/* Gaussian-process log marginal likelihood, device-resident:
+ *   logml[k] = -1/2 d_k^T M_k^-1 d_k - 1/2 log det M_k - n/2 log(2 pi),     M_k = B_k + diag(c_k)
+ * B: batch*n*n (SPD, column-major, stride n*n; only the lower triangle is read); c, d: batch*n; dCs may be NULL (M = B); logml: batch
+ * scalars. No input is modified; neither the inverse nor M is written to memory. dInfo as above (logml[k] is NaN for info != 0).
+ * n <= 96: one bordered MFMA tile kernel (d rides as a border row, the corner ends as -d^T M^-1 d). Beyond, to n = 1024: composed
+ * from matinv_variance_batched (a = d, e = 0), the global-memory logdet kernel on B + diag c and a combining kernel. Asynchronous. */
+int matinv_logml_batched(int dtype, int n, const void *dBs, const void *dCs, const void *dDs, void *dLogml, size_t batch, int *dInfo,
+                         void *stream);
+/* Host-pointer form (packed; hCs and `info` optional). Synchronous. */
+int matinv_logml_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hLogml, size_t batch, int *info);
+
 /* Host-pointer convenience used by the reference-named *_gpu wrappers: allocate, H2D, invert, D2H, free.
  * `info` is an optional host int[batch]. Synchronous. */
 int matinv_inverse_batched_host(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info);
