@@ -155,7 +155,16 @@ __device__ __forceinline__ void note_nonpositive_first(unsigned long long &bad, 
 // SPD = true: symmetric blocked sweep for SPD input (see matinv_spd_tile_f64). Same arithmetic for D^-1 and Aop; the
 // acceptance test becomes "all four pivots of D positive" (they are the squares of the Cholesky diagonal), and the
 // stage of tile row ti also returns bsym[ti] = P[16ti + c][q], the B operand by symmetry (W[K, J] = W[J, K]^T).
-template <int NT, bool SPD = false, class T = double>
+//
+// GATED = true: stages 0-5 -- the LU factorisation of D, its four reciprocals and the two triangular solves -- compute numbers that
+// depend on the lane through q = lane >> 4 only, so they run in ONE lane per row of 16 (c == 0; EXEC narrowed by a compile-time lane
+// mask, restored inside each stage: no MFMA is ever issued under the narrowed mask; the reads of D from LDS included), and x0 .. x3
+// reach the other 15 lanes of the row by DPP row_newbcast:0 at the end of stage 5 (stage_gated below). Same operations on the same operands in the same order per value, hence the same bits;
+// a masked lane contributes a zero bit to `bad |= vcc` and the tested values are uniform per q, so the verdict is the same as well.
+constexpr unsigned long long PANEL_GATE_LANES = 0x0001000100010001ULL;  // lane 16 q, q = 0 .. 3
+constexpr int DPP_ROW_NEWBCAST0 = 0x150;                                 // LLVM DppCtrl: lane 0 of each row of 16
+
+template <int NT, bool SPD = false, class T = double, bool GATED = false>
 struct PanelSolve {
     typedef TileGeo<T> G;
     static constexpr int NSTAGE = 6 + NT;
@@ -172,6 +181,131 @@ struct PanelSolve {
     }
     __device__ __forceinline__ void stage(int s, const T *panel, int kb, int q, int c, T (&aop)[NT],
                                           T (&bsym)[NT], unsigned long long &bad)
+    {
+        if constexpr (GATED) {
+            if (s < 6) {
+                stage_gated(s, panel, kb, q, bad);
+                return;
+            }
+        }
+        stage_impl(s, panel, kb, q, c, aop, bsym, bad);
+    }
+
+    // Stages 0-5 of the GATED mode, fp64. Each piece is asm that narrows EXEC to PANEL_GATE_LANES on entry and restores it on exit, so
+    // the compiler sees straight-line code on ordinary values (a C++ branch per piece costs the headline kernel 48 VGPRs and 84 B of
+    // scratch) and no MFMA or register copy of its own can land under the narrowed mask. The LU factors overwrite d in place:
+    // d[i][j] = l_ij below the diagonal, u_ij on and above it; y becomes x. Operation for operation it is stage_impl's arithmetic.
+    // Hazards (nothing is padded inside an asm block): one wait state between v_rcp_f64 and the first use of its result; the LDS reads
+    // are waited for before the block ends; two wait states between the last write of x and the DPP reads that follow stage 5.
+#define MATINV_PS_BEGIN "s_and_saveexec_b64 %[save], %[lanes]\n\t"
+#define MATINV_PS_END "s_mov_b64 exec, %[save]"
+#define MATINV_PS_RCP(r, x) /* fast_rcp */                                                                                             \
+    "v_rcp_f64_e32 %[" #r "], %[" #x "]\n\ts_nop 0\n\t"                                                                               \
+    "v_fma_f64 %[e], -%[" #x "], %[" #r "], 1.0\n\tv_fmac_f64_e32 %[" #r "], %[" #r "], %[e]\n\t"                                     \
+    "v_fma_f64 %[e], -%[" #x "], %[" #r "], 1.0\n\tv_fmac_f64_e32 %[" #r "], %[" #r "], %[e]\n\t"
+#define MATINV_PS_FMA(d, a, b, c) "v_fma_f64 %[" #d "], -%[" #a "], %[" #b "], %[" #c "]\n\t" /* d = c - a b */
+#define MATINV_PS_MUL(d, a, b) "v_mul_f64 %[" #d "], %[" #a "], %[" #b "]\n\t"
+#define MATINV_PS_TEST(v) "v_cmp_nle_f64_e64 vcc, |%[" #v "]|, 4.0\n\ts_or_b64 %[bad], %[bad], vcc\n\t"
+    __device__ __forceinline__ void stage_gated(int s, const T *panel, int kb, int q, unsigned long long &bad)
+    {
+        static_assert(!GATED || (sizeof(T) == 8 && !SPD), "the gated pivot-block solve is written for fp64 and the multiplier test");
+        static_assert(TILE_TAU == 4.0, "the asm below hard-codes the inline constant 4.0");
+        const unsigned long long lanes = PANEL_GATE_LANES;
+        unsigned long long save;
+        T e;
+        if (s == 0) {
+            // row i of D: 32 bytes at panel + 32 (4 kb + i)  (f64: trow(rK, i) = 4 rK + i)
+            const unsigned addr = (unsigned)(unsigned long long)panel + 128u * (unsigned)kb;
+            typename G::vec2 d0a, d0b, d1a, d1b, d2a, d2b, d3a, d3b;
+            asm volatile(MATINV_PS_BEGIN
+                         "ds_read_b128 %[d0a], %[addr]\n\tds_read_b128 %[d0b], %[addr] offset:16\n\t"
+                         "ds_read_b128 %[d1a], %[addr] offset:32\n\tds_read_b128 %[d1b], %[addr] offset:48\n\t"
+                         "ds_read_b128 %[d2a], %[addr] offset:64\n\tds_read_b128 %[d2b], %[addr] offset:80\n\t"
+                         "ds_read_b128 %[d3a], %[addr] offset:96\n\tds_read_b128 %[d3b], %[addr] offset:112\n\t"
+                         "s_waitcnt lgkmcnt(0)\n\t" MATINV_PS_END
+                         : [d0a] "=&v"(d0a), [d0b] "=&v"(d0b), [d1a] "=&v"(d1a), [d1b] "=&v"(d1b), [d2a] "=&v"(d2a), [d2b] "=&v"(d2b),
+                           [d3a] "=&v"(d3a), [d3b] "=&v"(d3b), [save] "=&s"(save)
+                         : [lanes] "s"(lanes), [addr] "v"(addr)
+                         : "scc", "memory");
+            d[0][0] = d0a[0], d[0][1] = d0a[1], d[0][2] = d0b[0], d[0][3] = d0b[1];
+            d[1][0] = d1a[0], d[1][1] = d1a[1], d[1][2] = d1b[0], d[1][3] = d1b[1];
+            d[2][0] = d2a[0], d[2][1] = d2a[1], d[2][2] = d2b[0], d[2][3] = d2b[1];
+            d[3][0] = d3a[0], d[3][1] = d3a[1], d[3][2] = d3b[0], d[3][3] = d3b[1];
+            asm volatile(MATINV_PS_BEGIN MATINV_PS_RCP(r0, d00)
+                         MATINV_PS_MUL(l10, l10, r0) MATINV_PS_MUL(l20, l20, r0) MATINV_PS_MUL(l30, l30, r0) MATINV_PS_END
+                         : [r0] "=&v"(r0), [e] "=&v"(e), [l10] "+v"(d[1][0]), [l20] "+v"(d[2][0]), [l30] "+v"(d[3][0]), [save] "=&s"(save)
+                         : [lanes] "s"(lanes), [d00] "v"(d[0][0])
+                         : "scc");
+        } else if (s == 1) {
+            asm volatile(MATINV_PS_BEGIN
+                         MATINV_PS_FMA(u11, l10, d01, u11) MATINV_PS_FMA(u12, l10, d02, u12) MATINV_PS_FMA(u13, l10, d03, u13)
+                         MATINV_PS_FMA(a21, l20, d01, a21) MATINV_PS_FMA(a22, l20, d02, a22) MATINV_PS_FMA(a23, l20, d03, a23)
+                         MATINV_PS_FMA(a31, l30, d01, a31) MATINV_PS_FMA(a32, l30, d02, a32) MATINV_PS_FMA(a33, l30, d03, a33)
+                         MATINV_PS_RCP(r1, u11) MATINV_PS_END
+                         : [u11] "+v"(d[1][1]), [u12] "+v"(d[1][2]), [u13] "+v"(d[1][3]), [a21] "+v"(d[2][1]), [a22] "+v"(d[2][2]),
+                           [a23] "+v"(d[2][3]), [a31] "+v"(d[3][1]), [a32] "+v"(d[3][2]), [a33] "+v"(d[3][3]), [r1] "=&v"(r1),
+                           [e] "=&v"(e), [save] "=&s"(save)
+                         : [lanes] "s"(lanes), [l10] "v"(d[1][0]), [l20] "v"(d[2][0]), [l30] "v"(d[3][0]), [d01] "v"(d[0][1]),
+                           [d02] "v"(d[0][2]), [d03] "v"(d[0][3])
+                         : "scc");
+        } else if (s == 2) {
+            asm volatile(MATINV_PS_BEGIN
+                         MATINV_PS_MUL(l21, l21, r1) MATINV_PS_MUL(l31, l31, r1)
+                         MATINV_PS_FMA(u22, l21, u12, u22) MATINV_PS_FMA(u23, l21, u13, u23)
+                         MATINV_PS_FMA(b32, l31, u12, b32) MATINV_PS_FMA(b33, l31, u13, b33)
+                         MATINV_PS_RCP(r2, u22)
+                         MATINV_PS_MUL(b32, b32, r2) MATINV_PS_FMA(b33, b32, u23, b33) MATINV_PS_END
+                         : [l21] "+v"(d[2][1]), [l31] "+v"(d[3][1]), [u22] "+v"(d[2][2]), [u23] "+v"(d[2][3]), [b32] "+v"(d[3][2]),
+                           [b33] "+v"(d[3][3]), [r2] "=&v"(r2), [e] "=&v"(e), [save] "=&s"(save)
+                         : [lanes] "s"(lanes), [r1] "v"(r1), [u12] "v"(d[1][2]), [u13] "v"(d[1][3])
+                         : "scc");
+        } else if (s == 3) {
+            // a zero / non-finite last pivot needs no test of its own: see stage_impl
+            asm volatile(MATINV_PS_BEGIN MATINV_PS_RCP(r3, u33)
+                         MATINV_PS_TEST(l10) MATINV_PS_TEST(l20) MATINV_PS_TEST(l30) MATINV_PS_TEST(l21) MATINV_PS_TEST(l31)
+                         MATINV_PS_TEST(l32) MATINV_PS_END
+                         : [r3] "=&v"(r3), [e] "=&v"(e), [bad] "+s"(bad), [save] "=&s"(save)
+                         : [lanes] "s"(lanes), [u33] "v"(d[3][3]), [l10] "v"(d[1][0]), [l20] "v"(d[2][0]), [l30] "v"(d[3][0]),
+                           [l21] "v"(d[2][1]), [l31] "v"(d[3][1]), [l32] "v"(d[3][2])
+                         : "vcc", "scc");
+        } else if (s == 4) {
+            // L y = e_q (y0 = e_q[0]); the right-hand side enters as the addend of the first FMA of its row
+            y0 = (q == 0) ? (T)1 : (T)0;
+            const T e1 = (q == 1) ? (T)1 : (T)0, e2 = (q == 2) ? (T)1 : (T)0, e3 = (q == 3) ? (T)1 : (T)0;
+            asm volatile(MATINV_PS_BEGIN
+                         MATINV_PS_FMA(y1, l10, y0, e1)
+                         MATINV_PS_FMA(y2, l20, y0, e2) MATINV_PS_FMA(y2, l21, y1, y2)
+                         MATINV_PS_FMA(y3, l30, y0, e3) MATINV_PS_FMA(y3, l31, y1, y3) MATINV_PS_FMA(y3, l32, y2, y3) MATINV_PS_END
+                         : [y1] "=&v"(y1), [y2] "=&v"(y2), [y3] "=&v"(y3), [save] "=&s"(save)
+                         : [lanes] "s"(lanes), [y0] "v"(y0), [e1] "v"(e1), [e2] "v"(e2), [e3] "v"(e3), [l10] "v"(d[1][0]),
+                           [l20] "v"(d[2][0]), [l30] "v"(d[3][0]), [l21] "v"(d[2][1]), [l31] "v"(d[3][1]), [l32] "v"(d[3][2])
+                         : "scc");
+        } else {
+            // U x = y, x1 .. x3 in place of y1 .. y3; then x0 .. x3 of lane 16 q to the whole row
+            asm volatile(MATINV_PS_BEGIN
+                         MATINV_PS_MUL(y3, y3, r3)
+                         MATINV_PS_FMA(y2, u23, y3, y2) MATINV_PS_MUL(y2, y2, r2)
+                         MATINV_PS_FMA(y1, u12, y2, y1) MATINV_PS_FMA(y1, u13, y3, y1) MATINV_PS_MUL(y1, y1, r1)
+                         MATINV_PS_FMA(x0, d01, y1, y0) MATINV_PS_FMA(x0, d02, y2, x0) MATINV_PS_FMA(x0, d03, y3, x0)
+                         MATINV_PS_MUL(x0, x0, r0) "s_nop 1\n\t" MATINV_PS_END
+                         : [x0] "=&v"(x0), [y1] "+v"(y1), [y2] "+v"(y2), [y3] "+v"(y3), [save] "=&s"(save)
+                         : [lanes] "s"(lanes), [y0] "v"(y0), [r0] "v"(r0), [r1] "v"(r1), [r2] "v"(r2), [r3] "v"(r3), [d01] "v"(d[0][1]),
+                           [d02] "v"(d[0][2]), [d03] "v"(d[0][3]), [u12] "v"(d[1][2]), [u13] "v"(d[1][3]), [u23] "v"(d[2][3])
+                         : "scc");
+            x0 = __builtin_amdgcn_update_dpp(x0, x0, DPP_ROW_NEWBCAST0, 0xf, 0xf, false);
+            x1 = __builtin_amdgcn_update_dpp(y1, y1, DPP_ROW_NEWBCAST0, 0xf, 0xf, false);
+            x2 = __builtin_amdgcn_update_dpp(y2, y2, DPP_ROW_NEWBCAST0, 0xf, 0xf, false);
+            x3 = __builtin_amdgcn_update_dpp(y3, y3, DPP_ROW_NEWBCAST0, 0xf, 0xf, false);
+        }
+    }
+#undef MATINV_PS_BEGIN
+#undef MATINV_PS_END
+#undef MATINV_PS_RCP
+#undef MATINV_PS_FMA
+#undef MATINV_PS_MUL
+#undef MATINV_PS_TEST
+    __device__ __forceinline__ void stage_impl(int s, const T *panel, int kb, int q, int c, T (&aop)[NT],
+                                               T (&bsym)[NT], unsigned long long &bad)
     {
         const int tK = kb >> 2, rK = kb & 3;
         const bool panel_lane = G::blk(c) == rK;
@@ -254,13 +388,13 @@ struct PanelSolve {
     }
 };
 
-template <int NT, class T>
+template <int NT, bool GATED = false, class T>
 __device__ __forceinline__ void panel_solve(const T *panel, int kb, int q, int c, T (&aop)[NT],
                                             unsigned long long &bad)
 {
-    PanelSolve<NT, false, T> ps;
+    PanelSolve<NT, false, T, GATED> ps;
 #pragma unroll
-    for (int s = 0; s < PanelSolve<NT, false, T>::NSTAGE; ++s) ps.stage(s, panel, kb, q, c, aop, bad);
+    for (int s = 0; s < PanelSolve<NT, false, T, GATED>::NSTAGE; ++s) ps.stage(s, panel, kb, q, c, aop, bad);
 }
 
 // ---- symmetric (lower-triangular tile storage) helpers, shared by the SPD inverse and the fused GP kernel ----------

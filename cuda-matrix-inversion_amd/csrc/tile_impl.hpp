@@ -45,6 +45,10 @@
 #include "tile_common.hpp"
 #include "tile_screen.hpp"
 
+#ifndef MATINV_TILE_GATED_PANEL
+#define MATINV_TILE_GATED_PANEL 1  // 0: the pivot-block solve in all 64 lanes (A/B builds)
+#endif
+
 namespace matinv {
 
 // ---- pieces of one block step ---------------------------------------------------------------------------------
@@ -204,6 +208,8 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
     // 16-byte access feeds two tiles and a 16-lane group covers 256 contiguous bytes. Nothing else in the kernel
     // depends on the relabelling (a symmetric permutation of the matrix: inv(P A P^T) = P inv(A) P^T).
     constexpr bool PAIRED = FULL && (NT % 2 == 0);
+    // the pivot-block solve in one lane per row of 16 (PanelSolve, GATED): the headline instantiation
+    constexpr bool GATED = MATINV_TILE_GATED_PANEL && sizeof(T) == 8 && NT == 4 && FULL && LOOKAHEAD && !EARLY;
     const int l = threadIdx.x;
 
     // accept-list form (behind the screening kernel below): in_list[0 .. *in_count)
@@ -268,7 +274,7 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
 #endif
             panel_to_lds<NT, T>(panel, acc, 0, q, c);
             wave_lds_sync();
-            panel_solve<NT>(panel, 0, q, c, aop, bad);
+            panel_solve<NT, GATED>(panel, 0, q, c, aop, bad);
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 // ragged n: a block step whose four columns are all identity padding changes nothing (pivot block I,
@@ -306,8 +312,8 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
                     wave_lds_sync();
                     __builtin_amdgcn_sched_barrier(0);
                     T aop_next[NT];
-                    PanelSolve<NT, false, T> ps;
-                    constexpr int NS = PanelSolve<NT, false, T>::NSTAGE;
+                    PanelSolve<NT, false, T, GATED> ps;
+                    constexpr int NS = PanelSolve<NT, false, T, GATED>::NSTAGE;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
                         // spread the remaining MFMAs evenly over the stages

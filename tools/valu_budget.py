@@ -16,6 +16,7 @@ ROWS = [
     ("v_mfma_*", lambda op, src: op.startswith("v_mfma")),
     ("v_fma/fmac/mul/rcp/add_f64", lambda op, src: re.match(r"v_(fma|fmac|mul|rcp|add)_f64", op) is not None),
     ("v_fma/fmac/mul/rcp/add_f32", lambda op, src: re.match(r"v_(fma|fmac|mul|rcp|add)_f32", op) is not None),
+    ("v_mov_*_dpp (lane broadcast)", lambda op, src: op.startswith("v_mov") and op.endswith("_dpp")),
     ("v_mov_b64 ..., 0", lambda op, src: op.startswith("v_mov_b64") and src == "0"),
     ("v_mov_b64 vX, vY (copy)", lambda op, src: op.startswith("v_mov_b64") and src.startswith("v[")),
     ("v_mov_b32 ..., 0 / const", lambda op, src: op.startswith("v_mov_b32") and not src.startswith(("v", "s"))),
