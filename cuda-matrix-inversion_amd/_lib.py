@@ -40,7 +40,7 @@ NATIVE_NAMES = [
     "matinv_comm_init_rank", "matinv_comm_destroy", "matinv_allgather_shards", "matinv_allgather_local", "matinv_allgather_local_after", "matinv_debug_rejects",
     "matinv_solve_batched", "matinv_solve_batched_ex", "matinv_solve_kernel_name", "matinv_solve_batched_host",
     "matinv_logdet_batched", "matinv_logdet_batched_ex", "matinv_logdet_kernel_name", "matinv_logdet_batched_host",
-    "matinv_logml_batched", "matinv_logml_batched_host",
+    "matinv_logml_batched", "matinv_logml_batched_host", "matinv_gp_kernel_name", "matinv_logml_kernel_name",
 ]
 GJ_NATURAL_FIRST, GJ_PIVOT, GJ_ADAPTIVE = 0, 1, 2
 
@@ -96,6 +96,10 @@ def lib() -> ctypes.CDLL:
     L.matinv_logml_batched.argtypes = [ci, ci, vp, vp, vp, vp, sz, vp, vp]
     L.matinv_logml_batched_host.restype = ci
     L.matinv_logml_batched_host.argtypes = [ci, ci, vp, vp, vp, vp, sz, vp]
+    L.matinv_gp_kernel_name.restype = ctypes.c_char_p
+    L.matinv_gp_kernel_name.argtypes = [ci, ci, ci]
+    L.matinv_logml_kernel_name.restype = ctypes.c_char_p
+    L.matinv_logml_kernel_name.argtypes = [ci, ci]
     L.matinv_select_kernel.restype = ci
     L.matinv_select_kernel.argtypes = [ci, ci, ci]
     L.matinv_kernel_name.restype = ctypes.c_char_p

@@ -360,6 +360,18 @@ def logdet_kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> s
     return _lib.lib().matinv_logdet_kernel_name(algo, code, n, kernel).decode()
 
 
+def gp_kernel_name(dtype, n: int, variance: bool = False) -> str:
+    """matinv_gp_kernel_name: the first kernel a fused mean / variance request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_gp_kernel_name(code, n, 1 if variance else 0).decode()
+
+
+def logml_kernel_name(dtype, n: int) -> str:
+    """matinv_logml_kernel_name: the first kernel a logml request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_logml_kernel_name(code, n).decode()
+
+
 mean_batched = calcluateMean
 variance_batched = calcluateVariance
 

@@ -88,6 +88,24 @@ int select_auto(int algo, int n)
     return MATINV_ERR_UNSUPPORTED;
 }
 
+// Does the forced family `kernel` (not AUTO) have a kernel for a full inversion of size n? The launcher below and matinv_kernel_name both
+// ask here, so a name is returned exactly where a launch would not be refused.
+template <class T>
+bool family_serves(int algo, int n, int kernel)
+{
+    const bool gj = algo == MATINV_ALGO_GAUSS_JORDAN;
+    switch (kernel) {
+    case MATINV_KERNEL_LDS: return lds_family_supports<T>(n);
+    case MATINV_KERNEL_ROWLANE: return rowlane_family_supports<T>(n);
+    case MATINV_KERNEL_TILE: return gj ? tile_family_supports<T>(n) : spd_tile_supports<T>(n);
+    case MATINV_KERNEL_GLOBAL: return global_family_supports<T>(n);
+    case MATINV_KERNEL_BLOCKED: return gj ? blocked_gj_supports(n) : blocked_inverse_supports(n);
+    case MATINV_KERNEL_TILEP: return gj && (tilep_supports(n) || tileq_supports(sizeof(T) == 8, n));
+    case MATINV_KERNEL_ROW: return gj && row_family_supports<T>(n);
+    default: return false;
+    }
+}
+
 template <class T>
 int inverse_dispatch(int algo, int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *dInfo, hipStream_t stream,
                      int kernel, int chol_phases = 7)
@@ -107,53 +125,54 @@ int inverse_dispatch(int algo, int n, BatchRef<const T> A, BatchRef<T> X, size_t
             return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
     }
     hipError_t e = hipErrorInvalidValue;
+    const bool serves = family_serves<T>(algo, n, kernel);
     switch (kernel) {
     case MATINV_KERNEL_LDS:
-        if (!lds_family_supports<T>(n)) return fail(MATINV_ERR_UNSUPPORTED, "LDS family: n=%d does not fit 160 KiB", n);
+        if (!serves) return fail(MATINV_ERR_UNSUPPORTED, "LDS family: n=%d does not fit 160 KiB", n);
         e = (algo == MATINV_ALGO_GAUSS_JORDAN) ? launch_gj_lds<T>(n, A, X, batch, dInfo, stream)
                                                : launch_chol_lds<T>(n, A, X, batch, dInfo, stream, chol_phases);
         break;
     case MATINV_KERNEL_ROWLANE:
-        if (!rowlane_family_supports<T>(n) || (algo == MATINV_ALGO_CHOLESKY && chol_phases != 7))
+        if (!serves || (algo == MATINV_ALGO_CHOLESKY && chol_phases != 7))
             return fail(MATINV_ERR_UNSUPPORTED, "rowlane family serves full inversions with n <= 16 only (n=%d)", n);
         e = (algo == MATINV_ALGO_CHOLESKY) ? launch_spd_rowlane<T>(n, A, X, batch, dInfo, stream)
                                            : launch_gj_rowlane<T>(n, A, X, batch, dInfo, stream);
         break;
     case MATINV_KERNEL_TILE:
         if (algo == MATINV_ALGO_CHOLESKY) {
-            if (!spd_tile_supports<T>(n) || chol_phases != 7)
+            if (!serves || chol_phases != 7)
                 return fail(MATINV_ERR_UNSUPPORTED, "tile family serves the full SPD inverse with n <= 192 (f64) / 256 (f32) only (n=%d)", n);
             e = launch_spd_tile<T>(n, A, X, batch, dInfo, stream);
             break;
         }
-        if (!tile_family_supports<T>(n))
+        if (!serves)
             return fail(MATINV_ERR_UNSUPPORTED, "tile family serves Gauss-Jordan with n <= 192 (f64) / 256 (f32) only (n=%d)", n);
         e = launch_gj_tile<T>(n, A, X, batch, dInfo, stream);
         break;
     case MATINV_KERNEL_GLOBAL:
-        if (!global_family_supports<T>(n) || chol_phases != 7)
+        if (!serves || chol_phases != 7)
             return fail(MATINV_ERR_UNSUPPORTED, "global family serves full inversions with n <= 1024 only (n=%d)", n);
         e = (algo == MATINV_ALGO_GAUSS_JORDAN) ? launch_gj_global<T>(n, A, X, batch, dInfo, stream)
                                                : launch_chol_global<T>(n, A, X, batch, dInfo, stream);
         break;
     case MATINV_KERNEL_BLOCKED:
         if (algo == MATINV_ALGO_GAUSS_JORDAN) {
-            if (!blocked_gj_supports(n)) return fail(MATINV_ERR_UNSUPPORTED, "blocked family: n=%d exceeds the limit 1024", n);
+            if (!serves) return fail(MATINV_ERR_UNSUPPORTED, "blocked family: n=%d exceeds the limit 1024", n);
             e = launch_gj_blocked<T>(n, A, X, batch, dInfo, stream);
             break;
         }
-        if (!blocked_inverse_supports(n) || chol_phases != 7)
+        if (!serves || chol_phases != 7)
             return fail(MATINV_ERR_UNSUPPORTED, "blocked family serves the full SPD inverse with n <= 1024 only (n=%d)", n);
         e = launch_chol_blocked<T>(n, A, X, batch, dInfo, stream);
         break;
     case MATINV_KERNEL_TILEP:
-        if (algo != MATINV_ALGO_GAUSS_JORDAN || !(tilep_supports(n) || tileq_supports(sizeof(T) == 8, n)))
+        if (!serves)
             return fail(MATINV_ERR_UNSUPPORTED, "pivoting tile family serves Gauss-Jordan with n <= 192 (f64) / 256 (f32) only (n=%d)", n);
         e = n > 128 ? launch_gj_tileq<T>(n, A, X, batch, dInfo, stream, nullptr, nullptr, nullptr, nullptr, nullptr)
                     : (n > 64 ? launch_gj_tilep4<T>(n, A, X, batch, dInfo, stream) : launch_gj_tilep<T>(n, A, X, batch, dInfo, stream));
         break;
     case MATINV_KERNEL_ROW:
-        if (algo != MATINV_ALGO_GAUSS_JORDAN || !row_family_supports<T>(n))
+        if (!serves)
             return fail(MATINV_ERR_UNSUPPORTED, "row family serves Gauss-Jordan with n <= 64 only (n=%d)", n);
         e = launch_gj_row<T>(n, A, X, batch, dInfo, stream);
         break;
@@ -611,6 +630,42 @@ int solve_host(int algo, int n, int nrhs, const void *hA, const void *hB, void *
     return MATINV_OK;
 }
 
+// Which kernel a fused mean / variance request takes (the name function and the launcher both ask here):
+//   n <= 16 the rowlane kernel; 16 < n <= 25 the two-rows-per-lane kernel, inverse folded in registers (r03);
+//   then the MFMA tile kernels, one to three wavefronts per item, lower tiles only: fp64 112 < n <= 176 on two wavefronts, 176 < n <= 192 on
+//   three (spd_tile2_impl.hpp), the SPD sweep with the bilinear form folded out of the accumulators where the bordered form no longer fits
+//   one wavefront (fp64 80 < n <= 112, fp32 96 < n <= 160), the bordered sweep below that. (r01 - r03 kept A/B switches to the older
+//   kernels these replaced -- MATINV_GP_TILE / _GP_SPD_TILE / _GP_TILE4 and a several-wavefront all-tiles pipeline kernel: gone in r04.)
+//   Beyond, measured: the LDS kernel wins while two workgroups fit a CU (f32 up to n = 137: 4.7e6 vs 3.6e6 items/s at 130) and, in f64,
+//   over its whole range (2.0e6 vs 1.75e6 at 130); with one f32 workgroup per CU the blocked path wins (3.1e6 vs 1.6e6 at 160).
+enum { GP_ROWLANE = 0, GP_ROWLANE2, GP_SPD_TILE2, GP_SPD_TILE, GP_TILE, GP_BLOCKED, GP_GLOBAL, GP_LDS };
+template <class T>
+int gp_route(int n)
+{
+    constexpr bool f64 = sizeof(T) == 8;
+    if (rowlane_family_supports<T>(n)) {
+        static const bool use_rowlane = []() {
+            const char *s = getenv("MATINV_GP_ROWLANE");  // A/B switch for profiling; default on
+            return !(s && *s == '0');
+        }();
+        if (use_rowlane) return GP_ROWLANE;
+    }
+    if (rowlane2_gp_use(f64, n)) return GP_ROWLANE2;
+    if (f64 && spd_tile2_supports(true, n)) return GP_SPD_TILE2;
+    if (gp_spd_tile_supports(f64, n)) return GP_SPD_TILE;
+    if (gp_tile_supports(f64, n)) return GP_TILE;
+    if (!lds_family_supports<T>(n) || (!f64 && n > 137)) {
+        if (!global_family_supports<T>(n)) return fail(MATINV_ERR_UNSUPPORTED, "pipeline: n=%d exceeds the limit 1024", n);
+        static const bool use_blocked = []() {
+            const char *s = getenv("MATINV_GP_BLOCKED");  // A/B switch for profiling; default on
+            return !(s && *s == '0');
+        }();
+        if (use_blocked) return GP_BLOCKED;
+        if (!lds_family_supports<T>(n)) return GP_GLOBAL;
+    }
+    return GP_LDS;
+}
+
 template <class T>
 int gp_dispatch(int n, const void *a, const void *B, const void *c, const void *d, const void *e_, void *out,
                 size_t batch, int *dInfo, void *stream, bool variance)
@@ -621,83 +676,27 @@ int gp_dispatch(int n, const void *a, const void *B, const void *c, const void *
     if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
     int rc = check_device();
     if (rc) return rc;
-    if (rowlane_family_supports<T>(n)) {
-        static const bool use_rowlane = []() {
-            const char *s = getenv("MATINV_GP_ROWLANE");  // A/B switch for profiling; default on
-            return !(s && *s == '0');
-        }();
-        if (use_rowlane) {
-            hipError_t er = launch_gp_rowlane<T>(n, static_cast<const T *>(a), static_cast<const T *>(B), static_cast<const T *>(c),
-                                                 variance ? nullptr : static_cast<const T *>(d), static_cast<const T *>(e_),
-                                                 static_cast<T *>(out), batch, dInfo, static_cast<hipStream_t>(stream));
-            if (er != hipSuccess) return fail_hip(er, "kernel launch");
-            return MATINV_OK;
-        }
+    const int route = gp_route<T>(n);
+    if (route < 0) return route;
+    const T *As = static_cast<const T *>(a), *Bs = static_cast<const T *>(B), *Cs = static_cast<const T *>(c);
+    const T *Ds = variance ? nullptr : static_cast<const T *>(d), *Es = static_cast<const T *>(e_);
+    T *o = static_cast<T *>(out);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipErrorInvalidValue;
+    switch (route) {
+    case GP_ROWLANE: e = launch_gp_rowlane<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
+    case GP_ROWLANE2: e = launch_gp_rowlane2<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
+    case GP_SPD_TILE2:
+        if constexpr (sizeof(T) == 8) e = launch_gp_spd_tile2(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st);
+        break;
+    case GP_SPD_TILE: e = launch_gp_spd_tile<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
+    case GP_TILE: e = launch_gp_tile<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
+    case GP_BLOCKED: e = launch_gp_blocked<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
+    case GP_GLOBAL: e = launch_gp_global<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
+    case GP_LDS:  // fp32 only: the fp64 tile kernels reach n = 192, the LDS kernel fits n <= 138, so gp_route<double> never ends here
+        if constexpr (sizeof(T) == 4) e = launch_gp_lds<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st);
+        break;
     }
-    if (rowlane2_gp_use(sizeof(T) == 8, n)) {  // 16 < n <= 25: the two-rows-per-lane kernel, inverse folded in registers (r03)
-        hipError_t er = launch_gp_rowlane2<T>(n, static_cast<const T *>(a), static_cast<const T *>(B), static_cast<const T *>(c),
-                                              variance ? nullptr : static_cast<const T *>(d), static_cast<const T *>(e_),
-                                              static_cast<T *>(out), batch, dInfo, static_cast<hipStream_t>(stream));
-        if (er != hipSuccess) return fail_hip(er, "kernel launch");
-        return MATINV_OK;
-    }
-    // MFMA tile kernels, one or two wavefronts per item, lower tiles only: fp64 112 < n <= 176 on two wavefronts, 176 < n <= 192 on three (spd_tile2_impl.hpp),
-    // the SPD sweep with the bilinear form folded out of the accumulators where the bordered form no longer fits one wavefront
-    // (fp64 80 < n <= 112, fp32 96 < n <= 160), the bordered sweep below that. (r01 - r03 kept A/B switches to the older kernels these
-    // replaced -- MATINV_GP_TILE / _GP_SPD_TILE / _GP_TILE4 and a several-wavefront all-tiles pipeline kernel: gone with it in r04.)
-    if constexpr (sizeof(T) == 8) {
-        if (spd_tile2_supports(true, n)) {
-            hipError_t e = launch_gp_spd_tile2(n, static_cast<const double *>(a), static_cast<const double *>(B), static_cast<const double *>(c),
-                                               variance ? nullptr : static_cast<const double *>(d), static_cast<const double *>(e_),
-                                               static_cast<double *>(out), batch, dInfo, static_cast<hipStream_t>(stream));
-            if (e != hipSuccess) return fail_hip(e, "kernel launch");
-            return MATINV_OK;
-        }
-    }
-    if (gp_spd_tile_supports(sizeof(T) == 8, n)) {
-        hipError_t e = launch_gp_spd_tile<T>(n, static_cast<const T *>(a), static_cast<const T *>(B), static_cast<const T *>(c),
-                                             variance ? nullptr : static_cast<const T *>(d), static_cast<const T *>(e_),
-                                             static_cast<T *>(out), batch, dInfo, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail_hip(e, "kernel launch");
-        return MATINV_OK;
-    }
-    if (gp_tile_supports(sizeof(T) == 8, n)) {
-        hipError_t e = launch_gp_tile<T>(n, static_cast<const T *>(a), static_cast<const T *>(B),
-                                         static_cast<const T *>(c), variance ? nullptr : static_cast<const T *>(d),
-                                         static_cast<const T *>(e_), static_cast<T *>(out), batch, dInfo,
-                                         static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return fail_hip(e, "kernel launch");
-        return MATINV_OK;
-    }
-    // measured: the LDS kernel wins while two workgroups fit a CU (f32 up to n = 137: 4.7e6 vs 3.6e6 items/s at 130) and, in
-    // f64, over its whole range (2.0e6 vs 1.75e6 at 130); with one f32 workgroup per CU the blocked path wins (3.1e6 vs 1.6e6
-    // at 160)
-    if (!lds_family_supports<T>(n) || (sizeof(T) == 4 && n > 137)) {
-        if (!global_family_supports<T>(n)) return fail(MATINV_ERR_UNSUPPORTED, "pipeline: n=%d exceeds the limit 1024", n);
-        static const bool use_blocked = []() {
-            const char *s = getenv("MATINV_GP_BLOCKED");  // A/B switch for profiling; default on
-            return !(s && *s == '0');
-        }();
-        if (use_blocked) {
-            hipError_t eb = launch_gp_blocked<T>(n, static_cast<const T *>(a), static_cast<const T *>(B),
-                                                 static_cast<const T *>(c), variance ? nullptr : static_cast<const T *>(d),
-                                                 static_cast<const T *>(e_), static_cast<T *>(out), batch, dInfo,
-                                                 static_cast<hipStream_t>(stream));
-            if (eb != hipSuccess) return fail_hip(eb, "kernel launch");
-            return MATINV_OK;
-        }
-        if (!lds_family_supports<T>(n)) {
-            hipError_t eg = launch_gp_global<T>(n, static_cast<const T *>(a), static_cast<const T *>(B),
-                                                static_cast<const T *>(c), variance ? nullptr : static_cast<const T *>(d),
-                                                static_cast<const T *>(e_), static_cast<T *>(out), batch, dInfo,
-                                                static_cast<hipStream_t>(stream));
-            if (eg != hipSuccess) return fail_hip(eg, "kernel launch");
-            return MATINV_OK;
-        }
-    }
-    hipError_t e = launch_gp_lds<T>(n, static_cast<const T *>(a), static_cast<const T *>(B), static_cast<const T *>(c),
-                                    variance ? nullptr : static_cast<const T *>(d), static_cast<const T *>(e_),
-                                    static_cast<T *>(out), batch, dInfo, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail_hip(e, "kernel launch");
     return MATINV_OK;
 }
@@ -847,6 +846,9 @@ int logml_check_args(int dtype, int n, const void *dBs, const void *dDs, const v
 
 // n <= 96: the bordered tile kernel. Beyond: the variance pipeline with a = d and e = 0 puts -d^T M^-1 d into scratch, the global
 // logdet kernel with diag = c the determinant (and info), a small kernel combines them.
+enum { LOGML_TILE = 0, LOGML_COMPOSED = 1 };
+int logml_route(int n) { return logdet_tile_supports(n) ? LOGML_TILE : LOGML_COMPOSED; }
+
 template <class T>
 int logml_dispatch(int n, const void *dBs, const void *dCs, const void *dDs, void *dLogml, size_t batch, int *dInfo, hipStream_t stream)
 {
@@ -854,10 +856,13 @@ int logml_dispatch(int n, const void *dBs, const void *dCs, const void *dDs, voi
     if (rc) return rc;
     const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *d = static_cast<const T *>(dDs);
     T *out = static_cast<T *>(dLogml);
-    if (logdet_tile_supports(n)) {
+    switch (logml_route(n)) {
+    case LOGML_TILE: {
         const hipError_t e = launch_logdet_tile<T>(n, true, B, (size_t)n * n, c, d, out, nullptr, batch, dInfo, stream);
         if (e != hipSuccess) return fail_hip(e, "logml launch");
         return MATINV_OK;
+    }
+    default: break;
     }
     // scratch: [e = 0 | (c = 0 when absent)] [var] [logdet]
     const size_t zeros = batch + (c ? 0 : batch * (size_t)n);
@@ -1058,7 +1063,10 @@ int matinv_select_kernel(int algo, int dtype, int n)
 const char *matinv_kernel_name(int algo, int dtype, int n, int kernel)
 {
     const bool f64 = dtype == MATINV_F64;
-    if (kernel == MATINV_KERNEL_AUTO) kernel = matinv_select_kernel(algo, dtype, n);
+    if (n < 1 || (dtype != MATINV_F64 && dtype != MATINV_F32) || (algo != MATINV_ALGO_GAUSS_JORDAN && algo != MATINV_ALGO_CHOLESKY)) return "";
+    if (kernel == MATINV_KERNEL_AUTO) kernel = f64 ? select_auto<double>(algo, n) : select_auto<float>(algo, n);
+    // "" exactly where inverse_dispatch answers MATINV_ERR_UNSUPPORTED (a forced family that has no kernel for this n)
+    if (!(f64 ? family_serves<double>(algo, n, kernel) : family_serves<float>(algo, n, kernel))) return "";
     switch (kernel) {
     case MATINV_KERNEL_LDS: return algo == MATINV_ALGO_CHOLESKY ? name_chol_lds(f64) : name_gj_lds(f64);
     case MATINV_KERNEL_ROWLANE: return algo == MATINV_ALGO_CHOLESKY ? name_spd_rowlane(f64, n) : name_gj_rowlane(f64, n);
@@ -1139,6 +1147,31 @@ const char *matinv_logdet_kernel_name(int algo, int dtype, int n, int kernel)
     if (route == LOGDET_ROW) return name_logdet_row(f64, n);
     if (route == LOGDET_GLOBAL) return name_logdet_global(f64, algo == MATINV_ALGO_CHOLESKY);
     return "";
+}
+
+const char *matinv_gp_kernel_name(int dtype, int n, int variance)
+{
+    (void)variance;  // mean and variance are one instantiation: the form is chosen by a null pointer at run time
+    if (n < 1 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    const bool f64 = dtype == MATINV_F64;
+    switch (f64 ? gp_route<double>(n) : gp_route<float>(n)) {
+    case GP_ROWLANE: return name_gp_rowlane(f64, n);
+    case GP_ROWLANE2: return name_gp_rowlane2(f64, n);
+    case GP_SPD_TILE2: return name_spd_tile2(true, n);
+    case GP_SPD_TILE: return name_gp_spd_tile(f64, n);
+    case GP_TILE: return name_gp_tile(f64, n);
+    case GP_BLOCKED: return f64 ? "matinv_bgp_update<double>" : "matinv_bgp_update<float>";  // the trailing update: most of the time
+    case GP_GLOBAL: return f64 ? "matinv_gp_global<double>" : "matinv_gp_global<float>";
+    case GP_LDS: return name_gp_lds(f64);
+    default: return "";
+    }
+}
+
+const char *matinv_logml_kernel_name(int dtype, int n)
+{
+    if (logml_check_args(dtype, n, nullptr, nullptr, nullptr, 0) != MATINV_OK || n > 1024) return "";
+    // composed: the variance pipeline does the work that grows fastest (then matinv_logdet_global and matinv_logml_combine)
+    return logml_route(n) == LOGML_TILE ? name_logdet_tile(dtype == MATINV_F64, true, n) : matinv_gp_kernel_name(dtype, n, 1);
 }
 
 int matinv_logdet_batched_host(int algo, int dtype, int n, const void *hA, void *hLogAbsDet, void *hSign, size_t batch, int *info)

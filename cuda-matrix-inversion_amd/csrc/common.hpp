@@ -137,6 +137,7 @@ const char *name_spd_rowlane(bool f64, int n);
 template <class T>
 hipError_t launch_gp_rowlane(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
                              int *info, hipStream_t stream);
+const char *name_gp_rowlane(bool f64, int n);
 template <class T>
 bool rowlane_family_supports(int n);
 // natural-order pass of the Gauss-Jordan entry point for 16 < n <= 32: the ROWLANE design with two rows per lane
@@ -280,6 +281,7 @@ const char *name_gp_tile(bool f64, int n);
 hipError_t debug_note_rejects(const int *work_count, hipStream_t stream);
 long long debug_rejects(bool reset);
 bool gp_spd_tile_supports(bool f64, int n);
+const char *name_gp_spd_tile(bool f64, int n);
 int spd_onewave_max(bool f64);  // largest n of the one-wavefront symmetric sweep (fp64 112, fp32 160)
 // fp32 9 x 9 / 10 x 10 lower tiles on one wavefront (spd_wide_f32_kernels.hip, gp_spd_wide_f32_kernels.hip): the kernel launch only, ws = [count, list...]
 hipError_t enqueue_spd_tile_wide_f32(int n, BatchRef<const float> A, BatchRef<float> X, unsigned grid, unsigned b, int *info, int *ws,

@@ -183,7 +183,7 @@ hipError_t launch_gp_tile(int n, const T *As, const T *Bs, const T *Cs, const T 
     if (batch == 0) return hipSuccess;
     return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
         const unsigned grid = tile_grid(batch, 8u), b = (unsigned)batch;
-        with_tile<1, 6>(tile_shape(n), [&](auto NT, auto FULL) {
+        with_tile<1, (sizeof(T) == 8 ? 5 : 6)>(tile_shape(n), [&](auto NT, auto FULL) {
             if constexpr (sizeof(T) == 8)
                 hipLaunchKernelGGL((matinv_gp_tile_f64<NT, FULL>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
             else

@@ -518,13 +518,15 @@ hipError_t launch_gp_lds_worklist(int n, const T *As, const T *Bs, const T *Cs, 
     template hipError_t launch_chol_lds<T>(int, BatchRef<const T>, BatchRef<T>, size_t, int *, hipStream_t, int);     \
     template hipError_t launch_chol_lds_worklist<T>(int, BatchRef<const T>, BatchRef<T>, const int *, const int *,    \
                                                     int *, hipStream_t);                                              \
-    template hipError_t launch_gp_lds<T>(int, const T *, const T *, const T *, const T *, const T *, T *, size_t,     \
-                                         int *, hipStream_t);                                                         \
     template hipError_t launch_gp_lds_worklist<T>(int, const T *, const T *, const T *, const T *, const T *, T *,    \
                                                   const int *, const int *, int *, hipStream_t);
 INST(double)
 INST(float)
 #undef INST
+// whole-batch form of the pipeline kernel: fp32 only (in fp64 the MFMA tile kernels serve every n that fits the LDS; the work-list form
+// above stays their fallback in both precisions)
+template hipError_t launch_gp_lds<float>(int, const float *, const float *, const float *, const float *, const float *, float *, size_t,
+                                         int *, hipStream_t);
 
 const char *name_gj_lds(bool f64) { return f64 ? "matinv_gj_lds<double>" : "matinv_gj_lds<float>"; }
 const char *name_chol_lds(bool f64) { return f64 ? "matinv_chol_lds<double>" : "matinv_chol_lds<float>"; }

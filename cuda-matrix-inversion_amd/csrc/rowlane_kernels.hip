@@ -443,13 +443,14 @@ template hipError_t launch_gp_rowlane<float>(int, const float *, const float *, 
                                              float *, size_t, int *, hipStream_t);
 
 // as rocprofv3 prints the instantiations (default template arguments spelled out)
-static const char *rowlane_name(bool f64, int n, bool spd)
+static const char *rowlane_name(bool f64, int n, bool spd, bool gp = false)
 {
     static thread_local char buf[80];
-    snprintf(buf, sizeof buf, "matinv_gj_rowlane<%s, %d, %s, %s, false>", f64 ? "double" : "float", n <= 8 ? 8 : 16,
-             (n == 8 || n == 16) ? "true" : "false", spd ? "true" : "false");
+    snprintf(buf, sizeof buf, "matinv_gj_rowlane<%s, %d, %s, %s, %s>", f64 ? "double" : "float", n <= 8 ? 8 : 16,
+             (n == 8 || n == 16) ? "true" : "false", spd ? "true" : "false", gp ? "true" : "false");
     return buf;
 }
+const char *name_gp_rowlane(bool f64, int n) { return rowlane_name(f64, n, true, true); }
 const char *name_spd_rowlane(bool f64, int n) { return rowlane_name(f64, n, true); }
 const char *name_gj_rowlane(bool f64, int n) { return rowlane_name(f64, n, false); }
 

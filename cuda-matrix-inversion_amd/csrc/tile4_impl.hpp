@@ -288,8 +288,9 @@ template <class T, bool SPD>
 static hipError_t launch_tile4(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
 {
     if (!(tile4_supports(n) || (n > 128 && n <= t4_wide_limit(sizeof(T) == 8)))) return hipErrorInvalidValue;
-    // SPD sweep: only the sizes no lower-tile kernel serves (fp64 176 < n <= 192, fp32 160 < n <= 256) are instantiated since r04
-    if (SPD && (n + 15) / 16 < (sizeof(T) == 8 ? 12 : 11)) return hipErrorInvalidValue;
+    // SPD sweep: only the sizes no lower-tile kernel serves (fp32 160 < n <= 256; in fp64 none: the three-wave lower-tile kernel goes up
+    // to 192) are instantiated
+    if (SPD && (sizeof(T) == 8 || (n + 15) / 16 < 11)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
     // Gauss-Jordan: general batches go straight to the PIVOTING kernel of this size once a natural-order launch of this size
     // has seen most of its matrices rejected (tile_kernels.hip "natural order or pivot search?")
@@ -329,7 +330,7 @@ static hipError_t launch_tile4(int n, BatchRef<const T> A, BatchRef<T> X, size_t
                 else if constexpr (!SPD)
                     hipLaunchKernelGGL((matinv_gj_tile4_f32<NT, FULL, W, SPD>), dim3(grid), dim3(64 * W), 0, stream, A, X, info, n, b, ws, ws + 2,
                                        in_count, in_list);
-            } else if constexpr ((!F64 || NT <= 12) && (!SPD || NT >= (F64 ? 12 : 11))) {
+            } else if constexpr ((!F64 || NT <= 12) && (!SPD || (!F64 && NT >= 11))) {
                 // more than 8 x 8 tiles: run-time n only, f64 up to 12 x 12
                 if constexpr (F64)
                     hipLaunchKernelGGL((matinv_gj_tile4_f64<NT, false, NT, SPD>), dim3(grid), dim3(64 * NT), 0, stream, A, X, info, n, b, ws, ws + 2,

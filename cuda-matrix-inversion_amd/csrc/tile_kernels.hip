@@ -163,6 +163,14 @@ template bool spd_tile_supports<float>(int);
 int spd_onewave_max(bool f64) { return f64 ? 112 : 160; }
 bool gp_spd_tile_supports(bool f64, int n) { return n > (f64 ? 80 : 96) && n <= spd_onewave_max(f64); }
 
+// the tile count picks the instantiation (run-time n only): launch_gp_spd_tile and the two wide translation units
+const char *name_gp_spd_tile(bool f64, int n)
+{
+    static thread_local char buf[48];
+    snprintf(buf, sizeof buf, "matinv_gp_spd_tile_%s<%d>", f64 ? "f64" : "f32", (n + 15) / 16);
+    return buf;
+}
+
 template hipError_t launch_gp_spd_tile<double>(int, const double *, const double *, const double *, const double *, const double *, double *,
                                                size_t, int *, hipStream_t);
 
@@ -172,8 +180,7 @@ hipError_t launch_spd_tile<double>(int n, BatchRef<const double> A, BatchRef<dou
     if (!spd_tile_supports<double>(n)) return hipErrorInvalidValue;
     // one wavefront holds the lower triangle up to 6 x 6 tiles in 256 registers (two waves per SIMD) and 7 x 7 in VGPRs + AGPRs
     // (one wave per SIMD, r03; before that 7 x 7 spilled: 5.8e6 inv/s at 112 x 112 against 9.9e6 on four wavefronts)
-    if (spd_tile2_supports(true, n)) return launch_spd_tile2(n, A, X, batch, info, stream);  // 112 < n <= 128: two waves, lower tiles
-    if (n > 112) return launch_spd_tile4<double>(n, A, X, batch, info, stream);  // 176 < n <= 192: one wavefront per tile column
+    if (spd_tile2_supports(true, n)) return launch_spd_tile2(n, A, X, batch, info, stream);  // 112 < n <= 192: two / three waves, lower tiles
     if (batch == 0) return hipSuccess;
     return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
         const TileShape s = spd_tile_shape(true, n);

@@ -111,7 +111,8 @@ int matinv_inverse_batched_ex(int algo, int dtype, int n, const void *dA, size_t
 /* Which family MATINV_KERNEL_AUTO resolves to (a matinv_kernel), or a negative status. */
 int matinv_select_kernel(int algo, int dtype, int n);
 
-/* Name of the __global__ function a (algo, dtype, n, kernel) request launches -- the name rocprofv3 reports. */
+/* Name of the __global__ function a (algo, dtype, n, kernel) request launches -- the name rocprofv3 reports ("" for a request that
+ * matinv_inverse_batched_ex would refuse: a forced family without a kernel for this n, n beyond 1024). Pure host logic. */
 const char *matinv_kernel_name(int algo, int dtype, int n, int kernel);
 
 /* Batched linear solve X_k = A_k^-1 B_k without forming the inverse in memory (for 16 < n <= 64 and nrhs <= 16).
@@ -150,6 +151,9 @@ int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, cons
                         void *dMeans, size_t batch, int *dInfo, void *stream);
 int matinv_variance_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dEs,
                             void *dVars, size_t batch, int *dInfo, void *stream);
+/* Name of the first __global__ function a mean (variance == 0) or variance request launches ("" for a request that would be refused).
+ * Both forms run the same instantiation. Pure host logic. */
+const char *matinv_gp_kernel_name(int dtype, int n, int variance);
 
 /* Batched log-determinant: sign_k * exp(logabsdet_k) = det A_k, without ever forming the determinant (it may overflow or underflow
  * the number format; log|det| does not).
@@ -186,6 +190,8 @@ int matinv_logdet_batched_host(int algo, int dtype, int n, const void *hA, void 
  * from matinv_variance_batched (a = d, e = 0), the global-memory logdet kernel on B + diag c and a combining kernel. Asynchronous. */
 int matinv_logml_batched(int dtype, int n, const void *dBs, const void *dCs, const void *dDs, void *dLogml, size_t batch, int *dInfo,
                          void *stream);
+/* Name of the first __global__ function a logml request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_logml_kernel_name(int dtype, int n);
 /* Host-pointer form (packed; hCs and `info` optional). Synchronous. */
 int matinv_logml_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hLogml, size_t batch, int *info);
 
