@@ -631,39 +631,23 @@ int solve_host(int algo, int n, int nrhs, const void *hA, const void *hB, void *
 }
 
 // Which kernel a fused mean / variance request takes (the name function and the launcher both ask here):
-//   n <= 16 the rowlane kernel; 16 < n <= 25 the two-rows-per-lane kernel, inverse folded in registers (r03);
+//   n <= 16 the rowlane kernel; 16 < n <= 25 the two-rows-per-lane kernel, inverse folded in registers;
 //   then the MFMA tile kernels, one to three wavefronts per item, lower tiles only: fp64 112 < n <= 176 on two wavefronts, 176 < n <= 192 on
 //   three (spd_tile2_impl.hpp), the SPD sweep with the bilinear form folded out of the accumulators where the bordered form no longer fits
-//   one wavefront (fp64 80 < n <= 112, fp32 96 < n <= 160), the bordered sweep below that. (r01 - r03 kept A/B switches to the older
-//   kernels these replaced -- MATINV_GP_TILE / _GP_SPD_TILE / _GP_TILE4 and a several-wavefront all-tiles pipeline kernel: gone in r04.)
-//   Beyond, measured: the LDS kernel wins while two workgroups fit a CU (f32 up to n = 137: 4.7e6 vs 3.6e6 items/s at 130) and, in f64,
-//   over its whole range (2.0e6 vs 1.75e6 at 130); with one f32 workgroup per CU the blocked path wins (3.1e6 vs 1.6e6 at 160).
-enum { GP_ROWLANE = 0, GP_ROWLANE2, GP_SPD_TILE2, GP_SPD_TILE, GP_TILE, GP_BLOCKED, GP_GLOBAL, GP_LDS };
+//   one wavefront (fp64 80 < n <= 112, fp32 96 < n <= 160), the bordered sweep below that;
+//   beyond the tile kernels (fp64 n > 192, fp32 n > 160) the blocked Cholesky path, up to n = 1024.
+enum { GP_ROWLANE = 0, GP_ROWLANE2, GP_SPD_TILE2, GP_SPD_TILE, GP_TILE, GP_BLOCKED };
 template <class T>
 int gp_route(int n)
 {
     constexpr bool f64 = sizeof(T) == 8;
-    if (rowlane_family_supports<T>(n)) {
-        static const bool use_rowlane = []() {
-            const char *s = getenv("MATINV_GP_ROWLANE");  // A/B switch for profiling; default on
-            return !(s && *s == '0');
-        }();
-        if (use_rowlane) return GP_ROWLANE;
-    }
-    if (rowlane2_gp_use(f64, n)) return GP_ROWLANE2;
+    if (rowlane_family_supports<T>(n)) return GP_ROWLANE;
+    if (rowlane2_supports(n)) return GP_ROWLANE2;
     if (f64 && spd_tile2_supports(true, n)) return GP_SPD_TILE2;
     if (gp_spd_tile_supports(f64, n)) return GP_SPD_TILE;
     if (gp_tile_supports(f64, n)) return GP_TILE;
-    if (!lds_family_supports<T>(n) || (!f64 && n > 137)) {
-        if (!global_family_supports<T>(n)) return fail(MATINV_ERR_UNSUPPORTED, "pipeline: n=%d exceeds the limit 1024", n);
-        static const bool use_blocked = []() {
-            const char *s = getenv("MATINV_GP_BLOCKED");  // A/B switch for profiling; default on
-            return !(s && *s == '0');
-        }();
-        if (use_blocked) return GP_BLOCKED;
-        if (!lds_family_supports<T>(n)) return GP_GLOBAL;
-    }
-    return GP_LDS;
+    if (!global_family_supports<T>(n)) return fail(MATINV_ERR_UNSUPPORTED, "pipeline: n=%d exceeds the limit 1024", n);
+    return GP_BLOCKED;
 }
 
 template <class T>
@@ -692,10 +676,6 @@ int gp_dispatch(int n, const void *a, const void *B, const void *c, const void *
     case GP_SPD_TILE: e = launch_gp_spd_tile<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
     case GP_TILE: e = launch_gp_tile<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
     case GP_BLOCKED: e = launch_gp_blocked<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
-    case GP_GLOBAL: e = launch_gp_global<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st); break;
-    case GP_LDS:  // fp32 only: the fp64 tile kernels reach n = 192, the LDS kernel fits n <= 138, so gp_route<double> never ends here
-        if constexpr (sizeof(T) == 4) e = launch_gp_lds<T>(n, As, Bs, Cs, Ds, Es, o, batch, dInfo, st);
-        break;
     }
     if (e != hipSuccess) return fail_hip(e, "kernel launch");
     return MATINV_OK;
@@ -1161,8 +1141,6 @@ const char *matinv_gp_kernel_name(int dtype, int n, int variance)
     case GP_SPD_TILE: return name_gp_spd_tile(f64, n);
     case GP_TILE: return name_gp_tile(f64, n);
     case GP_BLOCKED: return f64 ? "matinv_bgp_update<double>" : "matinv_bgp_update<float>";  // the trailing update: most of the time
-    case GP_GLOBAL: return f64 ? "matinv_gp_global<double>" : "matinv_gp_global<float>";
-    case GP_LDS: return name_gp_lds(f64);
     default: return "";
     }
 }

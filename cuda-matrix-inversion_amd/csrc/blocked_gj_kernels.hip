@@ -598,19 +598,9 @@ size_t blocked_workspace_cap()
 
 bool blocked_gj_supports(int n) { return n >= 1 && n <= 1024; }
 
-// smallest n that takes the two-level scheme (MFMA updates); below it: one level, rank-32 vector-ALU updates. MATINV_BGJ_TWO_LEVEL_MIN
-// overrides (A/B switch). r02: 384. r03: 224 at first (general input, f64: 256^2 2.25e5 -> 2.55e5 inv/s, 320^2 1.18e5 -> 1.49e5; f32
-// 320^2 1.80e5 -> 2.00e5; 200^2 equal), then 160 once the MFMA update ran at six waves per SIMD: 193^2 / 200^2 / 216^2
-// 3.25e5 / 3.15e5 / 2.88e5 -> 4.11e5 / 4.15e5 / 3.83e5
-int blocked_gj_two_level_min()
-{
-    static const int v = []() {
-        const char *s = getenv("MATINV_BGJ_TWO_LEVEL_MIN");
-        const int e = s && *s ? atoi(s) : 0;
-        return e > 0 ? e : 160;
-    }();
-    return v;
-}
+// smallest n that takes the two-level scheme (MFMA updates); below it: one level, rank-32 vector-ALU updates (how 160 was arrived at:
+// DESIGN.md, "Retired switches")
+int blocked_gj_two_level_min() { return 160; }
 
 template <class T>
 static hipError_t launch_gj_blocked_small(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
@@ -675,13 +665,6 @@ hipError_t launch_gj_blocked(int n, BatchRef<const T> A, BatchRef<T> X, size_t b
     const unsigned g = (unsigned)((n + BGJ_TILE - 1) / BGJ_TILE);
     // (128 x 128 workgroup tiles were used for fp32 until r03; with 8-deep slabs the 64 x 64 tile at six waves per SIMD is faster
     // there too: 1.65e4 against 1.54e4 inv/s at 1024^2, 8.9e4 against 8.3e4 at 512^2)
-    // columns per block (a multiple of the sub-panel width, <= BGJ_NB): MATINV_BGJ_NB overrides (A/B switch)
-    static const int nb_env = []() {
-        const char *s = getenv("MATINV_BGJ_NB");
-        const int v = s && *s ? atoi(s) : 0;
-        return (v >= BGJ_PB && v <= BGJ_NB && v % BGJ_PB == 0) ? v : 0;
-    }();
-    const int nbw = nb_env ? nb_env : BGJ_NB;
     for (size_t first = 0; first < batch; first += chunk) {
         const unsigned b = (unsigned)((batch - first < chunk) ? batch - first : chunk);
         // A flat batch (one matrix after the other, the usual case) is read in place by the first block's kernels; only a pointer
@@ -699,8 +682,8 @@ hipError_t launch_gj_blocked(int n, BatchRef<const T> A, BatchRef<T> X, size_t b
             cur = W0;
         }
         bool fused_finish = false;
-        for (int K0 = 0; K0 < n; K0 += nbw) {
-            const int bw = n - K0 < nbw ? n - K0 : nbw;
+        for (int K0 = 0; K0 < n; K0 += BGJ_NB) {
+            const int bw = n - K0 < BGJ_NB ? n - K0 : BGJ_NB;
             // the block's sub-panels, inside the block buffers: X0 = the block columns of cur, then P0, P1, P0, ...
             const T *pin = cur + (size_t)K0 * n;
             size_t in_stride = cur_stride;

@@ -41,21 +41,14 @@ static_assert(BGP_KS == SLAB_KS, "the update and product kernels stage slab_mma'
 
 // Leading dimension of a working copy with `rows` rows: padded so that one column is an ODD multiple of 256 bytes. With
 // ld = 2 n = 2048 doubles consecutive columns of a panel are 16 KiB apart and a 64-column panel lands on two of the 128
-// HBM channels; with the odd multiple the columns walk through all of them. MATINV_BGP_PAD=0: unpadded (A/B measurements).
+// HBM channels; with the odd multiple the columns walk through all of them.
 template <class T>
-__host__ __device__ __forceinline__ int bgp_ld_padded(int rows)
+static int bgp_ld(int rows)
 {
     int units = (int)(((size_t)rows * sizeof(T) + 255) / 256);
     units |= 1;
     return units * (256 / (int)sizeof(T));
 }
-static bool bgp_pad_on()
-{
-    static const bool on = [] { const char *s = getenv("MATINV_BGP_PAD"); return !(s && s[0] == '0'); }();
-    return on;
-}
-template <class T>
-static int bgp_ld(int rows) { return bgp_pad_on() ? bgp_ld_padded<T>(rows) : rows; }
 
 // working copy layout per item: (n + 2) rows x n columns, COLUMN-major with leading dimension ld >= n + 2 (bgp_ld):
 // element (r, c) at c*ld + r; rows n and n+1 are the border rows a^T and d^T (d = a for the variance).

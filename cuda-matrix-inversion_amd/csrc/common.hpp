@@ -120,10 +120,6 @@ hipError_t launch_chol_lds_worklist(int n, BatchRef<const T> A, BatchRef<T> X, c
 template <class T>
 hipError_t launch_chol_lds(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream,
                            int phases);
-// Ds == nullptr selects the variance form (needs Es); otherwise the mean form.
-template <class T>
-hipError_t launch_gp_lds(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
-                         int *info, hipStream_t stream);
 template <class T>
 bool lds_family_supports(int n);
 
@@ -140,10 +136,9 @@ hipError_t launch_gp_rowlane(int n, const T *As, const T *Bs, const T *Cs, const
 const char *name_gp_rowlane(bool f64, int n);
 template <class T>
 bool rowlane_family_supports(int n);
-// natural-order pass of the Gauss-Jordan entry point for 16 < n <= 32: the ROWLANE design with two rows per lane
+// natural-order pass of the Gauss-Jordan entry point for 16 < n <= 25: the ROWLANE design with two rows per lane
 // (rowlane2_kernels.hip); rejected matrices go to work_list like those of the natural-order tile kernels
-bool rowlane2_supports(int n);
-bool rowlane2_natural_use(bool f64, int n);
+bool rowlane2_supports(int n);  // 16 < n <= 25: where it replaces the MFMA tile kernels, natural-order pass and pipeline alike
 template <class T>
 hipError_t enqueue_gj_rowlane2(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream, int *work_count,
                                int *work_list);
@@ -152,7 +147,6 @@ const char *name_gj_rowlane2(bool f64, int n);
 template <class T>
 hipError_t launch_gp_rowlane2(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch, int *info,
                               hipStream_t stream);
-bool rowlane2_gp_use(bool f64, int n);  // where it replaces the MFMA tile pipeline kernel (16 < n <= 25; MATINV_ROWLANE2_GP=0: nowhere)
 const char *name_gp_rowlane2(bool f64, int n);
 template <class T>
 hipError_t enqueue_gp_rowlane2(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch, int *info,
@@ -192,9 +186,6 @@ template <class T>
 hipError_t launch_gj_global(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream);
 template <class T>
 hipError_t launch_chol_global(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream);
-template <class T>
-hipError_t launch_gp_global(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
-                            int *info, hipStream_t stream);
 const char *name_gj_global(bool f64);
 const char *name_chol_global(bool f64);
 
@@ -266,10 +257,12 @@ int set_gj_policy(int policy);  // returns the previous one
 
 const char *name_gj_rowlane(bool f64, int n);
 const char *name_gj_tile(bool f64, int n);
+// the LDS pipeline kernel over a device-side work list: finishes the items a tile or rowlane2 pipeline kernel rejected.
+// Ds == nullptr selects the variance form (needs Es); otherwise the mean form.
 template <class T>
 hipError_t launch_gp_lds_worklist(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out,
                                   const int *work_count, const int *work_list, int *info, hipStream_t stream);
-// fused GP scalars on the MFMA tile layout, one wavefront per item: f64 n <= 80, f32 n <= 96 (gp_tile_kernels.hip)
+// fused GP scalars on the MFMA tile layout, one wavefront per item: f64 16 < n <= 80, f32 16 < n <= 96 (gp_tile_kernels.hip)
 bool gp_tile_supports(bool f64, int n);
 template <class T>
 hipError_t launch_gp_tile(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
@@ -348,6 +341,5 @@ hipError_t launch_logml_combine(int n, const T *var, const T *logdet, T *logml, 
 
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
-const char *name_gp_lds(bool f64);
 
 }  // namespace matinv

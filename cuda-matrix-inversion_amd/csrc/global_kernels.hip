@@ -4,8 +4,7 @@
 // L2 / Infinity-Cache resident for the sizes in question) and only the pivot row and multiplier column of the current
 // step are staged in LDS. Same arithmetic as the LDS family:
 //   matinv_gj_global    in-place Gauss-Jordan with partial pivoting,
-//   matinv_chol_global  Cholesky factor, in-place triangular inverse, L^-T L^-1 (SPD input, lower triangle read),
-//   matinv_gp_global    fused mean / variance through the Cholesky factor and two forward substitutions.
+//   matinv_chol_global  Cholesky factor, in-place triangular inverse, L^-T L^-1 (SPD input, lower triangle read).
 // It is a functional path (2 n^3 * sizeof(T) bytes of cache traffic per matrix), not a tuned one: the blocked, MFMA-based
 // large-n path is listed as next in DESIGN.md.
 #include "common.hpp"
@@ -184,57 +183,6 @@ __global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(BatchRef<const 
 }
 
 template <class T>
-__global__ __launch_bounds__(GL_THREADS) void matinv_gp_global(const T *As, const T *Bs, const T *Cs, const T *Ds,
-                                                               const T *Es, T *out, int *info, int n, T *workspace)
-{
-    __shared__ T col[1024], u[1024], w[1024];
-    __shared__ T s_part[GL_THREADS / 64];
-    const size_t k_mat = blockIdx.x;
-    const T *B = Bs + k_mat * (size_t)n * n;
-    T *W = workspace + k_mat * (size_t)n * n;
-    const int t = threadIdx.x;
-    const bool variance = (Ds == nullptr);
-    const size_t nn = (size_t)n * n;
-    for (size_t e = t; e < nn; e += GL_THREADS) W[e] = B[e];
-    for (int i = t; i < n; i += GL_THREADS) {
-        u[i] = As[k_mat * n + i];
-        w[i] = variance ? (T)0 : Ds[k_mat * n + i];
-    }
-    __syncthreads();
-    for (int i = t; i < n; i += GL_THREADS) W[(size_t)i * n + i] += Cs[k_mat * n + i];
-    __syncthreads();
-    const int bad = gl_chol_factor(W, n, col);
-    if (bad) {
-        if (info && t == 0) info[k_mat] = bad;
-        if (t == 0) out[k_mat] = nan_of<T>();
-        return;
-    }
-    for (int k = 0; k < n; ++k) {  // forward substitution of both right-hand sides, column oriented
-        const T rk = (T)1 / W[(size_t)k * n + k];
-        const T uk = u[k] * rk, wk = w[k] * rk;
-        __syncthreads();
-        if (t == 0) { u[k] = uk; w[k] = wk; }
-        for (int i = k + 1 + t; i < n; i += GL_THREADS) {
-            const T l = W[(size_t)k * n + i];
-            u[i] -= l * uk;
-            w[i] -= l * wk;
-        }
-        __syncthreads();
-    }
-    T part = 0;
-    for (int i = t; i < n; i += GL_THREADS) part += u[i] * (variance ? u[i] : w[i]);
-    for (int off = 32; off >= 1; off >>= 1) part += __shfl_down(part, off);
-    if ((t & 63) == 0) s_part[t >> 6] = part;
-    __syncthreads();
-    if (t == 0) {
-        T q = 0;
-        for (int i = 0; i < GL_THREADS / 64; ++i) q += s_part[i];
-        out[k_mat] = variance ? Es[k_mat] - q : q;
-        if (info) info[k_mat] = 0;
-    }
-}
-
-template <class T>
 bool global_family_supports(int n) { return n >= 1 && n <= 1024; }
 template bool global_family_supports<double>(int);
 template bool global_family_supports<float>(int);
@@ -262,27 +210,9 @@ hipError_t launch_chol_global(int n, BatchRef<const T> A, BatchRef<T> X, size_t 
     return e != hipSuccess ? e : e2;
 }
 
-template <class T>
-hipError_t launch_gp_global(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
-                            int *info, hipStream_t stream)
-{
-    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
-    if (batch == 0) return hipSuccess;
-    T *ws = nullptr;
-    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), batch * (size_t)n * n * sizeof(T), stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(matinv_gp_global<T>, dim3((unsigned)batch), dim3(GL_THREADS), 0, stream, As, Bs, Cs, Ds, Es, out, info,
-                       n, ws);
-    e = hipGetLastError();
-    hipError_t e2 = scratch_free(ws, stream);
-    return e != hipSuccess ? e : e2;
-}
-
 #define INST(T)                                                                                                        \
     template hipError_t launch_gj_global<T>(int, BatchRef<const T>, BatchRef<T>, size_t, int *, hipStream_t);         \
-    template hipError_t launch_chol_global<T>(int, BatchRef<const T>, BatchRef<T>, size_t, int *, hipStream_t);       \
-    template hipError_t launch_gp_global<T>(int, const T *, const T *, const T *, const T *, const T *, T *, size_t,  \
-                                            int *, hipStream_t);
+    template hipError_t launch_chol_global<T>(int, BatchRef<const T>, BatchRef<T>, size_t, int *, hipStream_t);
 INST(double)
 INST(float)
 #undef INST

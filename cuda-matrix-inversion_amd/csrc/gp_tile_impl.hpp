@@ -10,7 +10,7 @@
 // tile storage) and reads the Schur complement -V^T M^-1 V out of the corner tile: mean = -G[0][1], var = e + G[0][0].
 // Tile columns left of the current pivot block are dead and skipped (no inverse is wanted), so the work is that of a
 // Cholesky factorisation with two right-hand sides; HBM traffic per item is the lower triangle of B plus three
-// vectors in, one scalar out. Not SPD (a pivot <= 0) -> device work list -> matinv_gp_lds (info reported there).
+// vectors in, one scalar out. Not SPD (a pivot <= 0) -> device work list -> matinv_gp_lds_worklist (info reported there).
 #pragma once
 #include <cstdio>
 
@@ -183,7 +183,7 @@ hipError_t launch_gp_tile(int n, const T *As, const T *Bs, const T *Cs, const T 
     if (batch == 0) return hipSuccess;
     return with_scratch_ints(batch + 1, 1, stream, [&](int *ws) {
         const unsigned grid = tile_grid(batch, 8u), b = (unsigned)batch;
-        with_tile<1, (sizeof(T) == 8 ? 5 : 6)>(tile_shape(n), [&](auto NT, auto FULL) {
+        with_tile<2, (sizeof(T) == 8 ? 5 : 6)>(tile_shape(n), [&](auto NT, auto FULL) {
             if constexpr (sizeof(T) == 8)
                 hipLaunchKernelGGL((matinv_gp_tile_f64<NT, FULL>), dim3(grid), dim3(64), 0, stream, As, Bs, Cs, Ds, Es, out, info, n, b, ws, ws + 1);
             else

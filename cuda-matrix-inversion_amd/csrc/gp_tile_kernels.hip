@@ -4,8 +4,9 @@
 namespace matinv {
 
 // one wavefront holds the bordered lower triangle of up to 7 x 7 tiles: fp32 n <= 96. In fp64 the last size spills 292 B per lane and the
-// SPD sweep with the bilinear form folded out of the accumulators (gp_spd_tile_supports) takes 80 < n <= 96: 6 x 6 tiles are not built
-bool gp_tile_supports(bool f64, int n) { return n >= 1 && n <= (f64 ? 80 : 96); }
+// SPD sweep with the bilinear form folded out of the accumulators (gp_spd_tile_supports) takes 80 < n <= 96: 6 x 6 tiles are not built.
+// n <= 16 belongs to the rowlane kernel: the one-tile instantiation is not built either
+bool gp_tile_supports(bool f64, int n) { return n > 16 && n <= (f64 ? 80 : 96); }
 
 template hipError_t launch_gp_tile<double>(int, const double *, const double *, const double *, const double *,
                                            const double *, double *, size_t, int *, hipStream_t);

@@ -402,16 +402,7 @@ __device__ __forceinline__ void gp_lds_one(const T *As, const T *Bs, const T *Cs
     }
 }
 
-template <class T>
-__global__ __launch_bounds__(LDS_THREADS) void matinv_gp_lds(const T *As, const T *Bs, const T *Cs, const T *Ds,
-                                                             const T *Es, T *out, int *info, int n)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    __shared__ T s_part[LDS_THREADS / 64];
-    gp_lds_one<T>(As, Bs, Cs, Ds, Es, out, info, n, blockIdx.x, smem_raw, s_part);
-}
-
-// the same over a device-side work list (fallback of matinv_gp_tile_f64)
+// over a device-side work list: the fallback for the items a tile or rowlane2 pipeline kernel rejects (not SPD)
 template <class T>
 __global__ __launch_bounds__(LDS_THREADS) void matinv_gp_lds_worklist(const T *As, const T *Bs, const T *Cs, const T *Ds,
                                                                       const T *Es, T *out, int *info, int n,
@@ -486,19 +477,6 @@ hipError_t launch_chol_lds(int n, BatchRef<const T> A, BatchRef<T> X, size_t bat
     return hipGetLastError();
 }
 template <class T>
-hipError_t launch_gp_lds(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out, size_t batch,
-                         int *info, hipStream_t stream)
-{
-    if (!lds_family_supports<T>(n)) return hipErrorInvalidValue;
-    if (batch == 0) return hipSuccess;
-    const size_t bytes = lds_bytes<T>(n);
-    hipError_t e = prepare_lds(matinv_gp_lds<T>, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(matinv_gp_lds<T>, dim3((unsigned)batch), dim3(LDS_THREADS), bytes, stream, As, Bs, Cs, Ds, Es,
-                       out, info, n);
-    return hipGetLastError();
-}
-template <class T>
 hipError_t launch_gp_lds_worklist(int n, const T *As, const T *Bs, const T *Cs, const T *Ds, const T *Es, T *out,
                                   const int *work_count, const int *work_list, int *info, hipStream_t stream)
 {
@@ -523,13 +501,8 @@ hipError_t launch_gp_lds_worklist(int n, const T *As, const T *Bs, const T *Cs, 
 INST(double)
 INST(float)
 #undef INST
-// whole-batch form of the pipeline kernel: fp32 only (in fp64 the MFMA tile kernels serve every n that fits the LDS; the work-list form
-// above stays their fallback in both precisions)
-template hipError_t launch_gp_lds<float>(int, const float *, const float *, const float *, const float *, const float *, float *, size_t,
-                                         int *, hipStream_t);
 
 const char *name_gj_lds(bool f64) { return f64 ? "matinv_gj_lds<double>" : "matinv_gj_lds<float>"; }
 const char *name_chol_lds(bool f64) { return f64 ? "matinv_chol_lds<double>" : "matinv_chol_lds<float>"; }
-const char *name_gp_lds(bool f64) { return f64 ? "matinv_gp_lds<double>" : "matinv_gp_lds<float>"; }
 
 }  // namespace matinv

@@ -1,4 +1,4 @@
-// rowlane2_kernels.hip -- the natural-order pass of the Gauss-Jordan entry point for 16 < n <= 32.
+// rowlane2_kernels.hip -- the natural-order pass of the Gauss-Jordan entry point for 16 < n <= 25.
 //
 // Same design as rowlane_kernels.hip (rows in registers, pivot row folded into the FMA as a DPP row broadcast) with TWO rows
 // per lane and, like the natural-order tile kernels it stands in for, VERIFIED pivots instead of a search: a matrix in which
@@ -25,7 +25,6 @@
 // normalizeRow :47-57, transform_matrix :59-82) like the other families; MODE 2 calcluateMean / calcluateVariance
 // (src/gauss_bench.cu:127-265,275-409).
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "common.hpp"
 #include "tile_common.hpp"
@@ -280,20 +279,10 @@ __global__ __launch_bounds__(RL2_THREADS, rl2_occupancy(sizeof(T), NC, FULL)) vo
     }
 }
 
-bool rowlane2_supports(int n) { return n > 16 && n <= 32; }
-
-// Where this pass replaces the natural-order tile kernel. MATINV_ROWLANE2=0: nowhere, =2: everywhere it can run (A/B
-// measurements); default: where it measured faster.
-bool rowlane2_natural_use(bool f64, int n)
-{
-    static const int mode = [] { const char *s = getenv("MATINV_ROWLANE2"); return s ? atoi(s) : 1; }();
-    if (!rowlane2_supports(n) || mode == 0) return false;
-    if (mode == 2) return true;
-    // measured (100 k matrices, natural-order pass only, this kernel against matinv_gj_tile_*<2, ..>): fp64 n = 17 / 20 / 24 / 25
-    // 1.60 / 1.50 / 1.33 / 1.04 x, n = 28 / 32 0.85 / 0.98 x; fp32 1.52 / 1.65 / 1.52 / 1.24 x and 0.97 / 0.87 x
-    (void)f64;
-    return n <= 25;
-}
+// Where this pass replaces the natural-order tile kernel, and the MFMA tile pipeline kernel: the sizes at which it measured faster
+// (100 k matrices, natural-order pass only, this kernel against matinv_gj_tile_*<2, ..>): fp64 n = 17 / 20 / 24 / 25
+// 1.60 / 1.50 / 1.33 / 1.04 x, n = 28 / 32 0.85 / 0.98 x; fp32 1.52 / 1.65 / 1.52 / 1.24 x and 0.97 / 0.87 x
+bool rowlane2_supports(int n) { return n > 16 && n <= 25; }
 
 template <class T, int NC, bool FULL, int MODE = RL2_GJ>
 static hipError_t launch_rl2(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream, int *work_count,
@@ -341,7 +330,6 @@ hipError_t enqueue_gj_rowlane2(int n, BatchRef<const T> A, BatchRef<T> X, size_t
 {
     if (!rowlane2_supports(n)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    if (n == 32) return launch_rl2<T, 32, true>(n, A, X, batch, info, stream, work_count, work_list);
     if (n == 24) return launch_rl2<T, 24, true>(n, A, X, batch, info, stream, work_count, work_list);
     if (n < 24) return launch_rl2<T, 24, false>(n, A, X, batch, info, stream, work_count, work_list);
     return launch_rl2<T, 32, false>(n, A, X, batch, info, stream, work_count, work_list);
@@ -368,13 +356,6 @@ template hipError_t launch_gp_rowlane2<double>(int, const double *, const double
 template hipError_t launch_gp_rowlane2<float>(int, const float *, const float *, const float *, const float *, const float *, float *, size_t,
                                               int *, hipStream_t);
 
-// MATINV_ROWLANE2_GP=0: the pipeline of these sizes stays on the MFMA tile kernel (A/B switch)
-bool rowlane2_gp_use(bool f64, int n)
-{
-    static const bool on = [] { const char *s = getenv("MATINV_ROWLANE2_GP"); return !(s && *s == '0'); }();
-    return on && rowlane2_natural_use(f64, n);
-}
-
 const char *name_gp_rowlane2(bool f64, int n)
 {
     static thread_local char buf[80];
@@ -385,8 +366,7 @@ const char *name_gp_rowlane2(bool f64, int n)
 const char *name_gj_rowlane2(bool f64, int n)
 {
     static thread_local char buf[80];
-    snprintf(buf, sizeof buf, "matinv_gj_rowlane2<%s, %d, %s, 0>", f64 ? "double" : "float", n <= 24 ? 24 : 32,
-             (n == 24 || n == 32) ? "true" : "false");
+    snprintf(buf, sizeof buf, "matinv_gj_rowlane2<%s, %d, %s, 0>", f64 ? "double" : "float", n <= 24 ? 24 : 32, n == 24 ? "true" : "false");
     return buf;
 }
 

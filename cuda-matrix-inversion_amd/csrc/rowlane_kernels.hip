@@ -15,7 +15,6 @@
 // Replaces, for small n, the 3n launches of /root/reference/src/gauss/batched_invert.cu:84-95 (pivotRow :17-45,
 // normalizeRow :47-57, transform_matrix :59-82) with one launch that touches HBM once per element.
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "common.hpp"
 
@@ -387,11 +386,7 @@ static hipError_t launch_one(int n, BatchRef<const T> A, BatchRef<T> X, size_t b
     const size_t blocks = (waves + ROWLANE_THREADS / 64 - 1) / (ROWLANE_THREADS / 64);
     // persistent-style grid: as many 4-wave blocks as stay resident (one wave per SIMD per block), each wave strides
     // over the batch; every wave then gets within one iteration of the same work and always has a next matrix to prefetch
-    static const unsigned per_cu = []() {
-        const char *s = getenv("MATINV_ROWLANE_BLOCKS_PER_CU");  // tuning knob for profiling
-        return (unsigned)(s && atoi(s) > 0 ? atoi(s) : 0);
-    }();
-    const unsigned resident = 256u * (per_cu ? per_cu : (unsigned)rowlane_occupancy(sizeof(T), NP, FULL));
+    const unsigned resident = 256u * (unsigned)rowlane_occupancy(sizeof(T), NP, FULL);
     const unsigned grid = (unsigned)(blocks < resident ? blocks : resident);
     hipLaunchKernelGGL((matinv_gj_rowlane<T, NP, FULL, SPD, GP>), dim3(grid), dim3(ROWLANE_THREADS), 0, stream, A, X, info, n,
                        (unsigned)batch, gp);

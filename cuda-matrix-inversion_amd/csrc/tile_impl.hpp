@@ -718,7 +718,7 @@ hipError_t launch_gj_tile_natural(int n, BatchRef<const T> A, BatchRef<T> X, siz
 {
     constexpr bool F64 = sizeof(T) == 8;
     const TileShape s = tile_shape(n);
-    const bool rowlane2 = rowlane2_natural_use(F64, n);
+    const bool rowlane2 = rowlane2_supports(n);
     const bool screen = !rowlane2 && tile_policy_use_screen(F64, s.nt);
     return with_scratch_ints((screen ? 3 : 2) * batch + 4, 4, stream, [&](int *ws) {
         int *const rej_count = ws, *const sing_count = ws + 1, *const acc_count = ws + 2;

@@ -211,7 +211,7 @@ const char *name_spd_tile(bool f64, int n)
 const char *name_gj_tile(bool f64, int n)
 {
     if (n > 64) return name_tile4(f64, false, n);
-    if (rowlane2_natural_use(f64, n)) return name_gj_rowlane2(f64, n);
+    if (rowlane2_supports(n)) return name_gj_rowlane2(f64, n);
     // the instantiation the launcher takes without the screening pass (the default EARLY = false left out)
     const TileShape s = tile_shape(n);
     static thread_local char buf[48];

@@ -13,8 +13,9 @@ refused). This module asks for every n in 1 .. 1024 on every route and groups th
 A Case is one (route, name, n). cases() holds, for every name of every route, the first and the last n of each run of consecutive
 sizes that name serves -- for a partial-tile instantiation n % 16 == 1 and 15, for a FULL one its single n -- and, for names whose
 run is longer than a tile (LDS, GLOBAL, the blocked paths: no n in the name), the sizes inside the run at which the host code
-branches: the two-level threshold of the blocked Gauss-Jordan and the fp32 pipeline's switch from the LDS kernel to the blocked
-path between 137 and 138. tests/test_instantiations_cpu.py checks the list against the kernels compiled into the library,
+branches: the two-level threshold of the blocked Gauss-Jordan. The mean / variance routes also keep the fp32 sizes 137 and 138: no
+host branch, but the sizes either side of where the LDS fallback kernel (the pipeline kernels' rejects) drops to one workgroup per
+CU. tests/test_instantiations_cpu.py checks the list against the kernels compiled into the library,
 tests/test_gpu_instantiations.py runs it.
 """
 import contextlib
@@ -36,7 +37,7 @@ ALGOS = {"gj": GJ, "chol": CH}
 DTYPES = {"f64": F64, "f32": F32}
 LOGDET_FAMILIES = ("auto", "tile", "row", "global")
 SOLVE_FUSED_NRHS, SOLVE_COMPOSED_NRHS = (1, 16), 17
-PIPELINE_F32_LDS_MAX = 137  # gp_route: with one f32 workgroup per CU the blocked path wins
+PIPELINE_F32_LDS_MAX = 137  # last fp32 size at which two workgroups of the LDS fallback kernel (matinv_gp_lds_worklist) fit a CU
 
 # entry: inverse / solve / logdet / mean / variance / logml; algo, dtype, family: keys of the tables above (algo and family "" where
 # the entry point has none; for solve also "pivot": AUTO while matinv_set_gj_policy(PIVOT) holds); nrhs: 0 except for solve
@@ -133,7 +134,7 @@ def cases():
         picked = set()
         for first, last in runs(ns):
             picked.update((first, last))
-            if last - first > 16 or r.entry in ("mean", "variance"):  # no n in the name / gp_route's own switch: where the host branches
+            if last - first > 16 or r.entry in ("mean", "variance"):  # no n in the name: where the host branches; mean / variance: PIPELINE_F32_LDS_MAX
                 picked.update(n for n in internal_boundaries() if first < n < last)
         out += [Case(r, name, n) for n in sorted(picked)]
     return tuple(out)

@@ -30,7 +30,6 @@ from _instantiation_runner import (LEAD, Blocks, bits, info_buffer, read_info, r
                                    screened_cases)
 from test_gpu_logdet import U, check_logdet, check_logml, full_image, lower_image  # noqa: E402
 from test_gpu_solve import check_close  # noqa: E402
-from test_gpu_switches import WORKER as SWITCH_WORKER  # noqa: E402
 
 api = inst.api
 lib = pkg("_lib")
@@ -272,18 +271,3 @@ def test_screened_launches_give_the_same_bits(tmp_path):
         assert np.array_equal(screened[f"{i}i"], here[f"{i}i"]), (inst.case_id(c), "info")
         assert np.array_equal(screened[str(i)], here[str(i)]), (inst.case_id(c), "result bits")
 
-
-# Instantiations only an A/B switch of the environment reaches (the table of test_instantiations_cpu.py) at the sizes test_gpu_switches.py
-# does not have: one process per switch, its worker and its tolerances.
-SWITCH_ONLY = [
-    ({"MATINV_ROWLANE2": "2"}, ["gj_mixed:f32:32:13", "gj_mixed:f64:32:13"]),           # matinv_gj_rowlane2<T, 32, true, 0>
-    ({"MATINV_GP_ROWLANE": "0"}, ["mean:f32:16:13", "variance:f64:16:13", "mean:f64:1:13", "mean:f32:15:13"]),  # matinv_gp_tile_*<1, ..>
-    ({"MATINV_GP_BLOCKED": "0"}, ["mean:f64:193:5", "variance:f32:198:5", "mean:f32:161:5", "variance:f32:197:5"]),  # gp_global, gp_lds<float>
-]
-
-
-@pytest.mark.parametrize("setting", SWITCH_ONLY, ids=lambda s: ",".join(f"{k}={v}" for k, v in s[0].items()))
-def test_instantiations_behind_a_switch(setting):
-    env, checks = setting
-    p = subprocess.run([sys.executable, SWITCH_WORKER, *checks], capture_output=True, text=True, env=dict(os.environ, **env), timeout=300)
-    assert p.returncode == 0 and "switch-worker ok" in p.stdout, (p.stdout[-2000:], p.stderr[-4000:])

@@ -21,22 +21,9 @@ SETTINGS = [
     ({"MATINV_TILE_SCREEN": "1"}, ["gj_mixed:f64:64:90", "gj_mixed:f64:50:90", "gj_mixed:f32:64:90", "gj_mixed:f32:40:90", "gj_spd:f64:32:40",
                                    "gj_mixed:f64:100:45", "gj_mixed:f64:128:30", "gj_mixed:f64:160:18", "gj_mixed:f32:96:45", "gj_mixed:f32:200:18"]),
     ({"MATINV_TILE_SCREEN": "0"}, ["gj_mixed:f64:64:90", "gj_general:f64:50:40", "gj_mixed:f32:64:90", "gj_mixed:f64:112:30", "gj_mixed:f32:144:18"]),
-    # several small matrices per wavefront
-    ({"MATINV_ROWLANE_BLOCKS_PER_CU": "2"}, ["gj_spd:f64:8:500", "gj_general:f64:16:300", "gj_spd:f32:12:300"]),
-    ({"MATINV_ROWLANE2": "0"}, ["gj_spd:f64:20:60", "gj_mixed:f64:24:60", "gj_spd:f32:25:60"]),
-    ({"MATINV_ROWLANE2": "2"}, ["gj_spd:f64:28:60", "gj_mixed:f64:32:60", "gj_spd:f32:30:60"]),
-    ({"MATINV_ROWLANE2_GP": "0"}, ["mean:f64:20:60", "variance:f64:24:60", "mean:f32:18:60"]),
     # one wavefront per matrix
     ({"MATINV_TILE_GRID_MULT": "1"}, ["gj_spd:f64:64:5000", "chol:f64:48:5000", "mean:f64:64:5000"]),
-    # fused mean / variance dispatch
-    ({"MATINV_GP_ROWLANE": "0"}, ["mean:f64:8:100", "variance:f64:16:100", "mean:f32:12:100"]),
-    ({"MATINV_GP_BLOCKED": "0"}, ["mean:f64:136:20", "mean:f32:190:20", "variance:f64:130:20"]),
     # blocked multi-launch paths
-    ({"MATINV_BGJ_TWO_LEVEL_MIN": "1000"}, ["gj_general:f64:320:12", "gj_general:f32:400:8"]),
-    ({"MATINV_BGJ_TWO_LEVEL_MIN": "130"}, ["gj_general:f64:200:12", "gj_general:f32:260:8"]),
-    ({"MATINV_BGJ_NB": "64"}, ["gj_general:f64:320:12", "gj_general:f32:512:6"]),
-    ({"MATINV_BGJ_NB": "96"}, ["gj_general:f64:400:8"]),
-    ({"MATINV_BGP_PAD": "0"}, ["chol:f64:256:12", "mean:f64:320:12", "chol:f32:512:6"]),
     ({"MATINV_BGP_PAIRS": "0"}, ["chol:f64:320:40", "mean:f32:512:40"]),
     ({"MATINV_BGP_PAIRS": "1"}, ["chol:f64:320:6", "mean:f64:256:6"]),
     # fused pipeline, blocked path: Cholesky form forced on a few items / block-LDL^T form forced on many

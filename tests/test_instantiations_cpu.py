@@ -33,11 +33,6 @@ REACHED_OTHERWISE = {
     rf"matinv_(bgp|bldl|binv)_\w+<{T}.*>": "any BLOCKED Cholesky / blocked pipeline case",
     rf"matinv_solve_gemm<{T}>": "any composed solve case (nrhs 17)",
     rf"matinv_logml_combine<{T}>": "any logml case beyond the bordered tile kernel (n > 96)",
-    # kernels behind an A/B switch of the environment, read once per process: test_gpu_switches.py runs each in a process of its own
-    rf"matinv_gj_rowlane2<{T}, 32, true, 0>": "MATINV_ROWLANE2=2 at n = 32 (by default the tile kernel keeps 25 < n <= 32)",
-    rf"matinv_gp_tile_{F}<1, {B}>": "MATINV_GP_ROWLANE=0 at n <= 16 (by default the rowlane kernel serves the pipeline there)",
-    rf"matinv_gp_global<{T}>": "MATINV_GP_BLOCKED=0 beyond the LDS limit",
-    r"matinv_gp_lds<float>": "MATINV_GP_BLOCKED=0 at fp32 160 < n <= 197",
     r"matinv_segcopy": "the batching queue: test_binqueue / test_gpu_cli, not a size-dependent instantiation",
 }
 
@@ -124,6 +119,7 @@ def test_case_list_holds_both_ends_of_every_name():
     t = inst.blocked_gj_two_level_min()
     gj_blocked = {c.n for c in have if c.route == inst.Route("inverse", "gj", "f64", "blocked", 0)}
     assert {1, t - 1, t, inst.N_MAX} <= gj_blocked
+    # and the fp32 pipeline sizes either side of where its LDS fallback kernel drops to one workgroup per CU
     for entry in ("mean", "variance"):
         ns = {c.n for c in have if c.route == inst.Route(entry, "", "f32", "", 0)}
         assert {inst.PIPELINE_F32_LDS_MAX, inst.PIPELINE_F32_LDS_MAX + 1} <= ns

@@ -1,4 +1,4 @@
-"""Time the fused mean pipeline at large n (blocked multi-launch path vs the one-workgroup GLOBAL kernel)."""
+"""Time the fused mean pipeline at large n (the tile kernels' last sizes and the blocked multi-launch path), with a value check."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import importlib
@@ -28,5 +28,4 @@ for dtype in (torch.float32, torch.float64):
         want = np.einsum("bi,bi->b", a.reshape(batch, n)[:k].double().cpu().numpy(),
                          np.linalg.solve(M, d.reshape(batch, n)[:k].double().cpu().numpy()[..., None])[..., 0])
         err = (np.abs(out[:k].double().cpu().numpy() - want) / np.abs(want)).max()
-        print(f"{str(dtype):14s} n={n:5d} batch={batch:4d}  {dt*1e3:9.3f} ms  {batch/dt:10.1f} items/s  relerr {err:.2e}  "
-              f"blocked={os.environ.get('MATINV_GP_BLOCKED','1')}", flush=True)
+        print(f"{str(dtype):14s} n={n:5d} batch={batch:4d}  {dt*1e3:9.3f} ms  {batch/dt:10.1f} items/s  relerr {err:.2e}", flush=True)
