@@ -354,6 +354,64 @@ def logml_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray):
     return out, info
 
 
+def loo_batched(n, Bs, Cs, Ds, mean=None, var=None, logpl=None, batchSize=None, info=None):
+    """Leave-one-out cross-validation of a GP on device tensors (matinv_loo_batched; asynchronous on torch's current stream). With
+    M_k = B_k + diag c_k, kappa_i = [M^-1]_ii and alpha = M^-1 d: mean_i = d_i - alpha_i / kappa_i (the prediction at training point i
+    from the other n - 1), var_i = 1 / kappa_i, logpl = sum_i (1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i) - n/2 log(2 pi).
+    Cs may be None (M = B). Only B's lower triangle is read and no input is modified. mean, var: optional tensors of at least
+    batchSize*n elements, logpl: of at least batchSize (allocated when None; elements beyond are left alone).
+    Returns (mean, var, logpl)."""
+    import torch
+    _require_cuda(Bs, Cs, Ds, mean, var, logpl, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    if mean is None:
+        mean = torch.empty(batchSize * n, dtype=Bs.dtype, device=Bs.device)
+    if var is None:
+        var = torch.empty(batchSize * n, dtype=Bs.dtype, device=Bs.device)
+    if logpl is None:
+        logpl = torch.empty(batchSize, dtype=Bs.dtype, device=Bs.device)
+    if any(t.dtype != Bs.dtype for t in (Ds, mean, var, logpl)) or (Cs is not None and Cs.dtype != Bs.dtype):
+        raise TypeError("Bs, Cs, Ds, mean, var and logpl must have one dtype")
+    if any(t.numel() < batchSize * n for t in (Ds, mean, var)) or logpl.numel() < batchSize or (Cs is not None and Cs.numel() < batchSize * n):
+        raise ValueError("Cs, Ds, mean and var need batchSize*n elements, logpl batchSize")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_loo_batched(
+            _torch_dtype_code(Bs), n, ctypes.c_void_p(Bs.data_ptr()), ctypes.c_void_p(Cs.data_ptr()) if Cs is not None else None,
+            ctypes.c_void_p(Ds.data_ptr()), ctypes.c_void_p(mean.data_ptr()), ctypes.c_void_p(var.data_ptr()),
+            ctypes.c_void_p(logpl.data_ptr()), batchSize, ctypes.c_void_p(info.data_ptr()) if info is not None else None, _stream_ptr(Bs)))
+    return mean, var, logpl
+
+
+def loo_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray):
+    """matinv_loo_batched_host on numpy batches (packed; Cs may be None): returns (mean, var, logpl, info). Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Ds = np.ascontiguousarray(Ds)
+    Cs = None if Cs is None else np.ascontiguousarray(Cs)
+    if Ds.dtype != Bs.dtype or (Cs is not None and Cs.dtype != Bs.dtype):
+        raise TypeError("Bs, Cs and Ds must have one dtype")
+    batch = Bs.size // (n * n)
+    if Ds.size < batch * n or (Cs is not None and Cs.size < batch * n):
+        raise ValueError("Cs and Ds smaller than batch*n")
+    mean = np.empty(batch * n, dtype=Bs.dtype)
+    var = np.empty(batch * n, dtype=Bs.dtype)
+    logpl = np.empty(batch, dtype=Bs.dtype)
+    info = np.zeros(batch, dtype=np.int32)
+    _lib.check(_lib.lib().matinv_loo_batched_host(
+        _np_dtype_code(Bs.dtype), n, Bs.ctypes.data_as(ctypes.c_void_p), Cs.ctypes.data_as(ctypes.c_void_p) if Cs is not None else None,
+        Ds.ctypes.data_as(ctypes.c_void_p), mean.ctypes.data_as(ctypes.c_void_p), var.ctypes.data_as(ctypes.c_void_p),
+        logpl.ctypes.data_as(ctypes.c_void_p), batch, info.ctypes.data_as(ctypes.c_void_p)))
+    return mean, var, logpl, info
+
+
+def loo_kernel_name(dtype, n: int) -> str:
+    """matinv_loo_kernel_name: the kernel a leave-one-out request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_loo_kernel_name(code, n).decode()
+
+
 def logdet_kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> str:
     """matinv_logdet_kernel_name: the kernel a logdet request launches ("" when the request would be refused)."""
     code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)

@@ -888,6 +888,64 @@ int logml_host(int n, const void *hBs, const void *hCs, const void *hDs, void *h
     return MATINV_OK;
 }
 
+// ---- batched leave-one-out cross-validation of a GP (matinv_loo_batched) ---------------------------------------------------------------
+int loo_check_args(int dtype, int n, const void *dBs, const void *dDs, const void *dMean, const void *dVar, const void *dLogPL, size_t batch)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (!dBs || !dDs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dMean && !dVar && !dLogPL) return fail(MATINV_ERR_ARG, "no output requested (mean, var and logpl are all null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    return MATINV_OK;
+}
+
+// n <= 96: the LOO form of the one-wavefront SPD sweep. Beyond, to n = 1024: the LOO form of the global-memory Cholesky kernel.
+template <class T>
+int loo_dispatch(int n, const void *dBs, const void *dCs, const void *dDs, void *dMean, void *dVar, void *dLogPL, size_t batch, int *dInfo,
+                 hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *d = static_cast<const T *>(dDs);
+    T *mean = static_cast<T *>(dMean), *var = static_cast<T *>(dVar), *logpl = static_cast<T *>(dLogPL);
+    const hipError_t e = loo_tile_supports(n) ? launch_loo_tile<T>(n, B, c, d, mean, var, logpl, batch, dInfo, stream)
+                                              : launch_loo_global<T>(n, B, c, d, mean, var, logpl, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "loo launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int loo_host(int n, const void *hBs, const void *hCs, const void *hDs, void *hMean, void *hVar, void *hLogPL, size_t batch, int *info)
+{
+    const size_t vec = (size_t)n * batch, mat = vec * n;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dMean = nullptr, *dVar = nullptr, *dLogPL = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
+    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMean), vec * sizeof(T));
+    if (e == hipSuccess && hVar) e = staging_alloc(reinterpret_cast<void **>(&dVar), vec * sizeof(T));
+    if (e == hipSuccess && hLogPL) e = staging_alloc(reinterpret_cast<void **>(&dLogPL), batch * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = loo_dispatch<T>(n, dB, dC, dD, dMean, dVar, dLogPL, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMean, vec * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hVar) e = hipMemcpy(hVar, dVar, vec * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hLogPL) e = hipMemcpy(hLogPL, dLogPL, batch * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dMean), staging_free(dVar), staging_free(dLogPL);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "loo host<->device");
+    return MATINV_OK;
+}
+
 template <class T>
 int lu_kernel(int n)
 {
@@ -1176,6 +1234,31 @@ int matinv_logml_batched_host(int dtype, int n, const void *hBs, const void *hCs
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return logml_host<double>(n, hBs, hCs, hDs, hLogml, batch, info);
     return logml_host<float>(n, hBs, hCs, hDs, hLogml, batch, info);
+}
+
+int matinv_loo_batched(int dtype, int n, const void *dBs, const void *dCs, const void *dDs, void *dMean, void *dVar, void *dLogPL, size_t batch,
+                       int *dInfo, void *stream)
+{
+    int rc = loo_check_args(dtype, n, dBs, dDs, dMean, dVar, dLogPL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return loo_dispatch<double>(n, dBs, dCs, dDs, dMean, dVar, dLogPL, batch, dInfo, st);
+    return loo_dispatch<float>(n, dBs, dCs, dDs, dMean, dVar, dLogPL, batch, dInfo, st);
+}
+
+const char *matinv_loo_kernel_name(int dtype, int n)
+{
+    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return loo_tile_supports(n) ? name_loo_tile(dtype == MATINV_F64, n) : name_loo_global(dtype == MATINV_F64);
+}
+
+int matinv_loo_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hMean, void *hVar, void *hLogPL,
+                            size_t batch, int *info)
+{
+    int rc = loo_check_args(dtype, n, hBs, hDs, hMean, hVar, hLogPL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return loo_host<double>(n, hBs, hCs, hDs, hMean, hVar, hLogPL, batch, info);
+    return loo_host<float>(n, hBs, hCs, hDs, hMean, hVar, hLogPL, batch, info);
 }
 
 int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dDs,

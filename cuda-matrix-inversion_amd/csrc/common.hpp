@@ -339,6 +339,19 @@ const char *name_logdet_global(bool f64, bool spd);
 template <class T>
 hipError_t launch_logml_combine(int n, const T *var, const T *logdet, T *logml, size_t batch, hipStream_t stream);
 
+// Batched leave-one-out cross-validation of a GP (matinv_loo_batched): mean, var: batch * n, logpl: batch, each optional.
+// (a) the LOO form of the one-wavefront SPD sweep, n <= 96 (loo_tile_kernels.hip, loo_tile_f32_kernels.hip)
+bool loo_tile_supports(int n);
+template <class T>
+hipError_t launch_loo_tile(int n, const T *Bs, const T *Cs, const T *Ds, T *mean, T *var, T *logpl, size_t batch, int *info,
+                           hipStream_t stream);
+const char *name_loo_tile(bool f64, int n);
+// (b) the LOO form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_loo_global(int n, const T *Bs, const T *Cs, const T *Ds, T *mean, T *var, T *logpl, size_t batch, int *info,
+                             hipStream_t stream);
+const char *name_loo_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

@@ -220,4 +220,130 @@ INST(float)
 const char *name_gj_global(bool f64) { return f64 ? "matinv_gj_global<double>" : "matinv_gj_global<float>"; }
 const char *name_chol_global(bool f64) { return f64 ? "matinv_chol_global<double>" : "matinv_chol_global<float>"; }
 
+// ---- leave-one-out cross-validation of a GP, 96 < n <= 1024 (matinv_loo_batched behind loo_tile_impl.hpp) -------------------------
+// The LOO form of matinv_chol_global: an overload with one more template argument ("Leave-one-out cross-validation", says
+// why it carries that name). M = B + diag c (lower triangle read, c optional) is factored in a working copy in library scratch and
+// the factor inverted in place, as above; then instead of the product L^-T L^-1
+//     kappa_i = sum_{k >= i} (L^-1)_ki^2,      alpha = L^-T (L^-1 d)       (two triangular products through LDS vectors)
+//     mean_i = d_i - alpha_i / kappa_i,   var_i = 1 / kappa_i,   logpl = sum_i (1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i) - n/2 log(2 pi)
+// so neither M nor its inverse reaches caller memory. Not SPD: info = the failing column + 1 and every output NaN. Correct first, as
+// logdet_global_kernels.hip: speed is not a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x.
+template <class T>
+__device__ __forceinline__ T gl_log(T v);
+template <>
+__device__ __forceinline__ double gl_log<double>(double v) { return log(v); }
+template <>
+__device__ __forceinline__ float gl_log<float>(float v) { return logf(v); }
+
+template <class T, bool LOO>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Ds, T *mean, T *var, T *logpl, int *info,
+                                                                 int n, T *workspace, size_t first)
+{
+    static_assert(LOO, "the two-argument form is the leave-one-out kernel");
+    __shared__ T col[1024], vd[1024], vy[1024];
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    T *W = workspace + (size_t)blockIdx.x * n * n;
+    const int t = threadIdx.x;
+    const size_t nn = (size_t)n * n;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    for (int i = t; i < n; i += GL_THREADS) vd[i] = Ds[k_mat * n + i];
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        for (int i = t; i < n; i += GL_THREADS) {
+            if (mean) mean[k_mat * n + i] = nan_of<T>();
+            if (var) var[k_mat * n + i] = nan_of<T>();
+        }
+        if (t == 0) {
+            if (logpl) logpl[k_mat] = nan_of<T>();
+            if (info) info[k_mat] = bad;
+        }
+        return;
+    }
+    for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+        const T ajj = (T)1 / W[(size_t)j * n + j];
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+        __syncthreads();
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+            W[(size_t)j * n + i] = -s * ajj;
+        }
+        if (t == 0) W[(size_t)j * n + j] = ajj;
+        __syncthreads();
+    }
+    // y = L^-1 d: (L^-1)_kj sits at W[j*n + k]
+    for (int k = t; k < n; k += GL_THREADS) {
+        T s = 0;
+        for (int j = 0; j <= k; ++j) s += W[(size_t)j * n + k] * vd[j];
+        vy[k] = s;
+    }
+    __syncthreads();
+    // column i of L^-1 gives kappa_i and alpha_i
+    T term = 0;
+    for (int i = t; i < n; i += GL_THREADS) {
+        T kappa = 0, alpha = 0;
+        for (int k = i; k < n; ++k) {
+            const T w = W[(size_t)i * n + k];
+            kappa += w * w;
+            alpha += w * vy[k];
+        }
+        const T rk = (T)1 / kappa;
+        const T q = alpha * rk;
+        if (mean) mean[k_mat * n + i] = vd[i] - q;
+        if (var) var[k_mat * n + i] = rk;
+        term += (T)0.5 * gl_log<T>(kappa) - (T)0.5 * alpha * q;
+    }
+    // block sum of the terms on a fixed tree
+    col[t] = term;
+    __syncthreads();
+    for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+        if (t < off) col[t] += col[t + off];
+        __syncthreads();
+    }
+    if (t == 0) {
+        if (logpl) logpl[k_mat] = col[0] - (T)n * (T)0.91893853320467274178;
+        if (info) info[k_mat] = 0;
+    }
+}
+
+template <class T>
+hipError_t launch_loo_global(int n, const T *Bs, const T *Cs, const T *Ds, T *mean, T *var, T *logpl, size_t batch, int *info,
+                             hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_logdet_global)
+    const size_t mat = (size_t)n * n;
+    size_t chunk = blocked_workspace_cap() / (mat * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * mat * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Bs, Cs, Ds, mean, var, logpl, info,
+                           n, ws, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_loo_global<double>(int, const double *, const double *, const double *, double *, double *, double *, size_t, int *,
+                                              hipStream_t);
+template hipError_t launch_loo_global<float>(int, const float *, const float *, const float *, float *, float *, float *, size_t, int *,
+                                             hipStream_t);
+
+const char *name_loo_global(bool f64) { return f64 ? "matinv_chol_global<double, true>" : "matinv_chol_global<float, true>"; }
+
 }  // namespace matinv

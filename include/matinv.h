@@ -195,6 +195,26 @@ const char *matinv_logml_kernel_name(int dtype, int n);
 /* Host-pointer form (packed; hCs and `info` optional). Synchronous. */
 int matinv_logml_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hLogml, size_t batch, int *info);
 
+/* Leave-one-out cross-validation of a Gaussian process (Rasmussen & Williams 5.4.2), device-resident. With M_k = B_k + diag(c_k),
+ * kappa_i = [M^-1]_ii and alpha = M^-1 d:
+ *   mean[k*n + i] = d_i - alpha_i / kappa_i      the prediction at training point i from the other n - 1
+ *   var[k*n + i]  = 1 / kappa_i                  its predictive variance (of the observation: the noise c_i included)
+ *   logpl[k]      = sum_i (1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i) - n/2 log(2 pi)      the log pseudo-likelihood
+ * B: batch*n*n (SPD, column-major, stride n*n; only the lower triangle is read); c, d: batch*n; dCs may be NULL (M = B).
+ * dMean, dVar: batch*n, dLogPL: batch scalars; each may be NULL (all three NULL: MATINV_ERR_ARG), and which of them are requested
+ * does not change a bit of the others. No input is modified (outputs must not overlap inputs); neither M nor its inverse is written
+ * to caller memory; the result of matrix k depends on matrix k alone. dInfo (optional): 0, or the 1-based column of the first
+ * non-positive (or NaN) pivot -- every output of that matrix is then NaN. n <= 96: the LOO form of the one-wavefront SPD tile sweep
+ * (n^2/2 + 2n elements read, 2n + 1 written). Beyond, to n = 1024: the LOO form of the global-memory Cholesky kernel on a working
+ * copy in library scratch. Asynchronous, no host synchronisation. */
+int matinv_loo_batched(int dtype, int n, const void *dBs, const void *dCs, const void *dDs, void *dMean, void *dVar, void *dLogPL,
+                       size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a leave-one-out request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_loo_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional). Synchronous. */
+int matinv_loo_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hMean, void *hVar, void *hLogPL,
+                            size_t batch, int *info);
+
 /* Host-pointer convenience used by the reference-named *_gpu wrappers: allocate, H2D, invert, D2H, free.
  * `info` is an optional host int[batch]. Synchronous. */
 int matinv_inverse_batched_host(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info);
