@@ -11,6 +11,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 constexpr double TILE_TAU = 4.0;
+constexpr int TILE_TSTRIDE = 17;  // padded row stride of the 16 x 16 LDS transpose buffer of the lower-tile sweeps (conflict-free reads)
 
 // Scalar-type traits of the tile kernels. The two 16x16x4 MFMAs differ in their C/D lane map (checked on hardware with
 // tools/mfma_layout_check.hip):   f64: tile row = 4*reg + (lane>>4)      f32: tile row = 4*(lane>>4) + reg
@@ -164,7 +165,9 @@ __device__ __forceinline__ void note_nonpositive_first(unsigned long long &bad, 
 constexpr unsigned long long PANEL_GATE_LANES = 0x0001000100010001ULL;  // lane 16 q, q = 0 .. 3
 constexpr int DPP_ROW_NEWBCAST0 = 0x150;                                 // LLVM DppCtrl: lane 0 of each row of 16
 
-template <int NT, bool SPD = false, class T = double, bool GATED = false>
+// BSYM: the stages of the tile rows return bsym. It comes with SPD; the symmetric arm of the Gauss-Jordan kernel (gj_tile_body)
+// asks for it on its own: bsym AND the multiplier test, gated or not.
+template <int NT, bool SPD = false, class T = double, bool GATED = false, bool BSYM = SPD>
 struct PanelSolve {
     typedef TileGeo<T> G;
     static constexpr int NSTAGE = 6 + NT;
@@ -380,9 +383,11 @@ struct PanelSolve {
                 if (!SPD) note_fail(bad, v);
             }
             aop[ti] = v;
-            if (SPD) {
+            if (BSYM && SPD) {
                 const T w01 = (q & 1) ? w1 : w0, w23 = (q & 1) ? w3 : w2;
                 bsym[ti] = (q & 2) ? w23 : w01;
+            } else if (BSYM) {
+                bsym[ti] = w[q];  // one more LDS read in place of three selects on 64-bit values (408 v_cndmask_b32 per 64 x 64 matrix)
             }
         }
     }

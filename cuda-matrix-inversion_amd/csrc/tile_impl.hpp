@@ -36,6 +36,14 @@
 // (row_kernels.hip; the LDS kernel for n > 64) -- no host round trip. Diagonally dominant / SPD batches (the reference's fixtures,
 // tests/generate_inverse_matrices.m:12-18) never take the fallback.
 //
+// Symmetric input at 64 x 64 fp64 (MATINV_TILE_SYM_SWEEP): the Gauss-Jordan entry makes no symmetry promise to its caller, so the
+// kernel finds out. After the loads it compares every element with its mirror, bit for bit, in registers (tile_asymmetry). A matrix
+// whose two triangles agree -- the reference's fixtures R + R^T + n I, every covariance matrix -- takes the sweep of the Cholesky
+// entry point (spd_tile_body below) on its ten lower tiles, 10 MFMAs per block step instead of 16, under the acceptance test of
+// THIS kernel (multipliers <= TAU, no test of signs: symmetric indefinite input is served too); the upper tiles are rebuilt from
+// the lower ones at the end, so the result is exactly symmetric. Any other matrix takes the full sweep and gets the bits it always
+// got. Rejects of either arm go to the same work list.
+//
 // Replaces the 3n launches of /root/reference/src/gauss/batched_invert.cu:84-95.
 #include <stdio.h>
 #include <stdlib.h>
@@ -47,6 +55,10 @@
 
 #ifndef MATINV_TILE_GATED_PANEL
 #define MATINV_TILE_GATED_PANEL 1  // 0: the pivot-block solve in all 64 lanes (A/B builds)
+#endif
+
+#ifndef MATINV_TILE_SYM_SWEEP
+#define MATINV_TILE_SYM_SWEEP 1  // 0: bitwise-symmetric 64 x 64 fp64 input takes the full sweep like any other (A/B builds)
 #endif
 
 namespace matinv {
@@ -179,7 +191,162 @@ __device__ __forceinline__ void prep_operands(typename TileGeo<T>::vec4 (&acc)[N
 #undef MATINV_PREP_TAIL
 #undef MATINV_PREP_SAVE
 
+// ---- the symmetric arm of the 64 x 64 fp64 kernel (MATINV_TILE_SYM_SWEEP) ------------------------------------------------------
+// A bitwise-symmetric matrix has a symmetric inverse, and the sweep of spd_tile_body reaches it on the NT (NT + 1) / 2 lower tiles:
+// 10 MFMAs per block step instead of 16. gj_tile_body classifies every matrix after its loads and takes that sweep -- with the
+// Gauss-Jordan ACCEPTANCE test, not the Cholesky one -- when the matrix qualifies. The pieces:
+
+// asym |= ballot(bits of a != bits of b). An INTEGER compare: +0.0 / -0.0 differ, a NaN equals itself, so a matrix counts as
+// symmetric exactly when both triangles hold the same bits. Inline asm for the reason given at note_fail.
+__device__ __forceinline__ void note_differs(unsigned long long &asym, double a, double b)
+{
+    asm volatile("v_cmp_ne_u64_e64 vcc, %1, %2\n\ts_or_b64 %0, %0, vcc" : "+s"(asym) : "v"(a), "v"(b) : "vcc");
+}
+
+// Lanes in which some element differs from its mirror. The relabelling of PAIRED is a symmetric permutation, so the mirror of
+// lane (q, c), register r of tile (ti, tj) is lane (c & 3, 4 r + q), register c >> 2 of tile (tj, ti): one tile of each of the six
+// off-diagonal pairs, and each diagonal tile, goes through the padded LDS buffer and comes back transposed.
+template <int NT>
+__device__ __forceinline__ unsigned long long tile_asymmetry(double *tbuf, const v4d (&acc)[NT][NT], int q, int c)
+{
+    typedef TileGeo<double> G;
+    unsigned long long asym = 0;
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj <= ti; ++tj) {
+            // Wave-uniform early leave: a mismatch has been seen, the verdict is in. Without it a batch that is not symmetric pays all
+            // ten round trips before its sweep starts: R + n I, 100 000 matrices, 3.5 % slower than without the classification.
+            if (asym != 0) continue;
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tbuf[G::trow(r, q) * TILE_TSTRIDE + c] = acc[ti][tj][r];
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) note_differs(asym, tbuf[c * TILE_TSTRIDE + G::trow(r, q)], acc[tj][ti][r]);
+        }
+    return asym;
+}
+
+// Every tile of a 4 x 4 accumulator array as ONE 256-bit register tuple at this point of the program (no instruction). Without it
+// hipcc keeps the freshly loaded elements in separate register pairs through the classification and assembles the MFMA tuples of
+// both arms in front of the branch: two copies of the matrix alive at once, and scratch.
+__device__ __forceinline__ void pin_tiles(v4d (&acc)[4][4])
+{
+    asm volatile("" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[1][0]), "+v"(acc[1][1]),
+                      "+v"(acc[1][2]), "+v"(acc[1][3]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[2][2]), "+v"(acc[2][3]),
+                      "+v"(acc[3][0]), "+v"(acc[3][1]), "+v"(acc[3][2]), "+v"(acc[3][3]));
+}
+
+// (The block-step loop below -- the (a) / (b) order of the MFMAs and the event schedule that places the pieces of the next panel
+// between them -- exists three times: spd_tile_body below, loo_tile_body in loo_tile_impl.hpp, and here. A change of the look-ahead
+// schedule belongs in all three.)
+// The look-ahead sweep of spd_tile_body on the lower tiles of acc (the upper ones are not read), with the acceptance test of the
+// natural-order kernel: the six LU multipliers of each pivot block and every A-operand entry outside the pivot rows <= TAU, no test
+// of the pivots' sign -- a symmetric INDEFINITE matrix that passes is inverted here as well. Block step 0 reads the panel as it was
+// loaded, through the stages panel_solve runs: the same operations on the same values in the same order as the full sweep's first
+// block step and as the screening kernel (tile_screen.hpp), hence their verdict. Leaves W = -A^-1 in the lower tiles.
+template <int NT, bool GATED, class T>
+__device__ __forceinline__ void sym_tile_sweep(typename TileGeo<T>::vec4 (&acc)[NT][NT], T *panel, int q, int c, unsigned long long &bad)
+{
+    typedef TileGeo<T> G;
+    typedef PanelSolve<NT, false, T, GATED, true> PS;
+    constexpr int NKB = 4 * NT;
+    T aop[NT], bop[NT];
+    spd_panel_to_lds<NT, T>(panel, acc, 0, q, c);
+    wave_lds_sync();
+    {
+        PS ps0;
+#pragma unroll
+        for (int s = 0; s < PS::NSTAGE; ++s) ps0.stage(s, panel, 0, q, c, aop, bop, bad);
+    }
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb) {
+        spd_prep_operands<NT, T>(acc, bop, kb, q, c);
+        if (kb + 1 < NKB) {
+            const int tn = (kb + 1) >> 2;
+            // (a) the tiles the next panel is read from: column tn (ti >= tn) and row tn (tj < tn)
+#pragma unroll
+            for (int ti = tn; ti < NT; ++ti) acc[ti][tn] = G::mfma(aop[ti], bop[tn], acc[ti][tn]);
+#pragma unroll
+            for (int tj = 0; tj < tn; ++tj) acc[tn][tj] = G::mfma(aop[tn], bop[tj], acc[tn][tj]);
+            // (b) the other lower tiles between the pieces of the next panel, as in spd_tile_body
+            constexpr int NB = NT * (NT + 1) / 2 - NT;
+            constexpr int NS = PS::NSTAGE;
+            T aop_next[NT], bop_next[NT];
+            PS ps;
+            int count = 0, ev = 0;  // MFMAs of (b) issued so far; next event (0 = stage the panel, 1 + s = stage s)
+            auto run_events = [&](bool flush) {
+#pragma unroll
+                for (int e = 0; e < NS + 1; ++e) {
+                    const int lead = NB < 2 ? NB : 2;
+                    const int thr = (e == 0) ? lead : lead + ((NB - lead) * e) / NS;
+                    if (e == ev && (flush || thr <= count)) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (e == 0) {
+                            wave_lds_sync();
+                            spd_panel_to_lds<NT, T>(panel, acc, kb + 1, q, c);
+                            wave_lds_sync();
+                        } else {
+                            ps.stage(e - 1, panel, kb + 1, q, c, aop_next, bop_next, bad);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        ++ev;
+                    }
+                }
+            };
+            run_events(false);
+#pragma unroll
+            for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+                for (int tj = 0; tj <= ti; ++tj) {
+                    if (ti == tn || tj == tn) continue;
+                    acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
+                    ++count;
+                    run_events(false);
+                }
+            run_events(true);
+#pragma unroll
+            for (int ti = 0; ti < NT; ++ti) { aop[ti] = aop_next[ti]; bop[ti] = bop_next[ti]; }
+        } else {
+#pragma unroll
+            for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+                for (int tj = 0; tj <= ti; ++tj) acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
+        }
+    }
+}
+
+// W = -A^-1 in the lower tiles -> A^-1 in all of them: the sign flipped, the six upper tiles rebuilt as the transposes of their
+// mirrors, and the upper triangle of each diagonal tile taken from its lower one (the sweep keeps the two equal only up to
+// rounding), all through the padded LDS buffer. The result is bitwise symmetric.
+template <int NT>
+__device__ __forceinline__ void sym_tile_finish(double *tbuf, v4d (&acc)[NT][NT], int q, int c)
+{
+    typedef TileGeo<double> G;
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj <= ti; ++tj) {
+            acc[ti][tj] = -acc[ti][tj];
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tbuf[G::trow(r, q) * TILE_TSTRIDE + c] = acc[ti][tj][r];
+            wave_lds_sync();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double t = tbuf[c * TILE_TSTRIDE + G::trow(r, q)];
+                acc[tj][ti][r] = (ti != tj || G::trow(r, q) < c) ? t : acc[tj][ti][r];
+            }
+        }
+}
+
 // One matrix per wavefront; see the file header. T = double or float.
+// The 4 x 4-tile fp64 kernels (FULL, both values of EARLY) have two arms: loads -> classification -> [symmetric: sym_tile_sweep on
+// the lower tiles, sym_tile_finish | otherwise: the block steps below] -> stores / work list. Both arms end in the same store text,
+// expanded once per arm (see `leave` at the end of the body for why they do not meet in front of it). The arms share no per-lane
+// constant: the symmetric one launders its own copy of the lane coordinates. Figures, tools/kernel_regs.py: 222 VGPRs (EARLY: 224),
+// no scratch, no AGPRs; as a diamond that meets at one copy of the stores 256 VGPRs and 132 - 328 B of scratch.
 // (Tried, not kept: letting a matrix that has already failed the acceptance test skip the remaining block steps through
 // nested scalar branches after every fourth step -- no loop exit, accumulators dead on the rejected path. hipcc answers the
 // control flow with 256 VGPRs + 344 B of scratch in the headline kernel instead of 212 and none.)
@@ -210,6 +377,9 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
     constexpr bool PAIRED = FULL && (NT % 2 == 0);
     // the pivot-block solve in one lane per row of 16 (PanelSolve, GATED): the headline instantiation
     constexpr bool GATED = MATINV_TILE_GATED_PANEL && sizeof(T) == 8 && NT == 4 && FULL && LOOKAHEAD && !EARLY;
+    // the symmetric arm (see tile_asymmetry / sym_tile_sweep / sym_tile_finish above): both instantiations of the 64 x 64 fp64
+    // kernel, the one behind the screening pass included -- the arm is the same code in both, so they give the same bits
+    constexpr bool SYM = MATINV_TILE_SYM_SWEEP && sizeof(T) == 8 && NT == 4 && FULL && LOOKAHEAD;
     const int l = threadIdx.x;
 
     // accept-list form (behind the screening kernel below): in_list[0 .. *in_count)
@@ -265,12 +435,24 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
         unsigned long long bad = 0;  // wave-uniform: lanes that saw a multiplier above TAU (or NaN)
         T aop[NT], bop[NT];
 
+        // Symmetric input? Wave-uniform, decided in registers once the loads are in. The verdict has two ARMS, each a whole sweep
+        // that ends in the stores -- not a way out of the unrolled chain of block steps (see the early-exit notes above).
+        bool sym = false;
+#ifndef MATINV_TILE_LDST_ONLY
+        if constexpr (SYM) {
+            pin_tiles(acc);
+            sym = tile_asymmetry<NT>(panel, acc, q, c) == 0;
+        }
+#endif
+
         // -DMATINV_TILE_LDST_ONLY (tools/build_ldst_variant.sh, profiling only): no elimination at all -- the kernel's loads and
         // stores in their real access pattern and launch shape, to price what the memory side alone costs
 #ifdef MATINV_TILE_LDST_ONLY
         if (false) {
 #else
-        if (LOOKAHEAD) {
+        if (SYM && sym) {
+            // the symmetric arm: after the other one, below
+        } else if (LOOKAHEAD) {
 #endif
             panel_to_lds<NT, T>(panel, acc, 0, q, c);
             wave_lds_sync();
@@ -360,39 +542,69 @@ __device__ __forceinline__ void gj_tile_body(BatchRef<const T> Ain, BatchRef<T> 
 #endif
         }
 
-        if (bad == 0) {
-            if (PAIRED) {
-                const unsigned lane_off2 = (unsigned)(2 * G::trow(0, l >> 4) * N + 2 * (l & 15));
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-                    for (int u = 0; u < NT / 2; ++u)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const unsigned uoff = (unsigned)((32 * (ti >> 1) + 2 * G::trow(r, 0) + (ti & 1)) * N + 32 * u);
-                            vec2 v;
-                            v[0] = acc[ti][2 * u][r];
-                            v[1] = acc[ti][2 * u + 1][r];
-                            __builtin_nontemporal_store(v, reinterpret_cast<vec2 *>(X + uoff + lane_off2));
-                        }
-            } else {
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 16 * ti + G::trow(r, q), col = 16 * tj + c;
-                            const unsigned uoff = (unsigned)((16 * ti + G::trow(r, 0)) * n + 16 * tj);
-                            const bool edge = !FULL && (ti == NT - 1 || tj == NT - 1);
-                            if (!edge || (row < n && col < n)) X[uoff + lane_off] = acc[ti][tj][r];
-                        }
-            }
-            if (info && l == 0) info[mat] = 0;
-        } else if (l == 0) {
-            const int slot = atomicAdd(work_count, 1);
-            work_list[slot] = (int)mat;
+        // The way out: accepted -> the stores and info = 0, rejected -> the work list. The kernel with the symmetric arm leaves from
+        // each arm through its own copy of this text (a lambda). Meeting at ONE copy makes every tile live across both arms, and hipcc
+        // then assembles the MFMA register tuples of both in front of the branch: 256 VGPRs and 132 - 328 B of scratch, whatever
+        // pins the tiles. Every other instantiation keeps the text in line, as it was -- hence the macro: called as a lambda everywhere
+        // the same text changes the register figures of the ragged kernels (NT = 3: 177 -> 169 VGPRs, NT = 4: 256 + 100 B of scratch
+        // -> 247 and none), which were not measured here and therefore stay what they were. The lambda itself is declared in the
+        // instantiation with the arm only: declared and unused elsewhere it still moved register copies in the 48 x 48 kernel and
+        // changed the code, and the bits, of the fp32 kernels.
+#define MATINV_GJ_TILE_LEAVE                                                                                                \
+        if (bad == 0) {                                                                                                     \
+            if (PAIRED) {                                                                                                   \
+                const unsigned lane_off2 = (unsigned)(2 * G::trow(0, l >> 4) * N + 2 * (l & 15));                           \
+_Pragma("unroll")                                                                                                           \
+                for (int ti = 0; ti < NT; ++ti)                                                                             \
+_Pragma("unroll")                                                                                                           \
+                    for (int u = 0; u < NT / 2; ++u)                                                                        \
+_Pragma("unroll")                                                                                                           \
+                        for (int r = 0; r < 4; ++r) {                                                                       \
+                            const unsigned uoff = (unsigned)((32 * (ti >> 1) + 2 * G::trow(r, 0) + (ti & 1)) * N + 32 * u); \
+                            vec2 v;                                                                                         \
+                            v[0] = acc[ti][2 * u][r];                                                                       \
+                            v[1] = acc[ti][2 * u + 1][r];                                                                   \
+                            __builtin_nontemporal_store(v, reinterpret_cast<vec2 *>(X + uoff + lane_off2));                 \
+                        }                                                                                                   \
+            } else {                                                                                                        \
+_Pragma("unroll")                                                                                                           \
+                for (int ti = 0; ti < NT; ++ti)                                                                             \
+_Pragma("unroll")                                                                                                           \
+                    for (int tj = 0; tj < NT; ++tj)                                                                         \
+_Pragma("unroll")                                                                                                           \
+                        for (int r = 0; r < 4; ++r) {                                                                       \
+                            const int row = 16 * ti + G::trow(r, q), col = 16 * tj + c;                                     \
+                            const unsigned uoff = (unsigned)((16 * ti + G::trow(r, 0)) * n + 16 * tj);                      \
+                            const bool edge = !FULL && (ti == NT - 1 || tj == NT - 1);                                      \
+                            if (!edge || (row < n && col < n)) X[uoff + lane_off] = acc[ti][tj][r];                         \
+                        }                                                                                                   \
+            }                                                                                                               \
+            if (info && l == 0) info[mat] = 0;                                                                              \
+        } else if (l == 0) {                                                                                                \
+            const int slot = atomicAdd(work_count, 1);                                                                      \
+            work_list[slot] = (int)mat;                                                                                     \
         }
+        if constexpr (SYM) {
+            auto leave = [&]() {
+                MATINV_GJ_TILE_LEAVE
+            };
+            if (!sym) {
+                leave();
+            } else {
+                // lane coordinates of the arm's own: its per-lane constants are then formed inside it and do not live across the
+                // other arm, which has no register to spare for them
+                int qs = q, cs = c;
+                asm volatile("" : "+v"(qs), "+v"(cs));
+                wave_lds_sync();  // the transpose buffer becomes the panel
+                sym_tile_sweep<NT, MATINV_TILE_GATED_PANEL != 0, T>(acc, panel, qs, cs, bad);
+                wave_lds_sync();  // ... and the transpose buffer again
+                if (bad == 0) sym_tile_finish<NT>(panel, acc, qs, cs);  // wave-uniform; a reject goes to the work list as it is
+                leave();
+            }
+        } else {
+            MATINV_GJ_TILE_LEAVE
+        }
+#undef MATINV_GJ_TILE_LEAVE
         if (LOOKAHEAD) wave_lds_sync();  // the next matrix's first panel write must not pass this one's last reads
     }
 }
@@ -408,7 +620,9 @@ __global__ __launch_bounds__(64, 2) void matinv_gj_tile_f64(BatchRef<const doubl
                                                                                  int *work_count, int *work_list, const int *in_count,
                                                                                  const int *in_list)
 {
-    __shared__ __attribute__((aligned(16))) double panel[16 * NT * 4];  // [row][4 pivot columns]
+    // [row][4 pivot columns]; the symmetric arm also uses it as the padded 16 x 16 transpose buffer
+    constexpr bool SYM = MATINV_TILE_SYM_SWEEP && NT == 4 && FULL && LOOKAHEAD;
+    __shared__ __attribute__((aligned(16))) double panel[SYM && 16 * NT * 4 < 16 * TILE_TSTRIDE ? 16 * TILE_TSTRIDE : 16 * NT * 4];
     gj_tile_body<double, NT, FULL, LOOKAHEAD, EARLY>(Ain, Xout, info, n_rt, batch, work_count, work_list, panel, in_count, in_list);
 }
 
@@ -459,7 +673,7 @@ __device__ __forceinline__ void spd_tile_body(BatchRef<const T> Ain, BatchRef<T>
     typedef typename G::vec4 vec4;
     constexpr int N = 16 * NT;
     constexpr int NKB = 4 * NT;
-    constexpr int TSTRIDE = 17;  // padded row stride of the 16x16 transpose buffer (conflict-free reads)
+    constexpr int TSTRIDE = TILE_TSTRIDE;  // padded row stride of the 16x16 transpose buffer
     const int l = threadIdx.x;
 
     for (unsigned mat = blockIdx.x; mat < batch; mat += gridDim.x) {
