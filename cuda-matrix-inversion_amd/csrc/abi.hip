@@ -946,6 +946,73 @@ int loo_host(int n, const void *hBs, const void *hCs, const void *hDs, void *hMe
     return MATINV_OK;
 }
 
+// ---- gradients of the batched GP log marginal likelihood (matinv_logml_grad_batched) -------------------------------------------------
+int logml_grad_check_args(int dtype, int n, int nparam, const void *dBs, const void *dDs, const void *dDMs, const void *dGrad,
+                          const void *dGradC, const void *dAlpha, size_t batch)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (nparam < 0) return fail(MATINV_ERR_ARG, "nparam must be >= 0 (got %d)", nparam);
+    if (!dBs || !dDs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dGrad && !dGradC && !dAlpha) return fail(MATINV_ERR_ARG, "no output requested (grad, gradc and alpha are all null)");
+    if (dGrad && nparam < 1) return fail(MATINV_ERR_ARG, "grad requested with nparam = 0");
+    if (dGrad && !dDMs) return fail(MATINV_ERR_ARG, "grad requested without derivative matrices (dDMs is null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    return MATINV_OK;
+}
+
+// n <= 96: the gradient form of the one-wavefront SPD sweep. Beyond, to n = 1024: the gradient form of the global-memory Cholesky kernel.
+template <class T>
+int logml_grad_dispatch(int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad, void *dGradC,
+                        void *dAlpha, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *d = static_cast<const T *>(dDs);
+    const T *dM = static_cast<const T *>(dDMs);
+    T *grad = static_cast<T *>(dGrad), *gradc = static_cast<T *>(dGradC), *alpha = static_cast<T *>(dAlpha);
+    const hipError_t e = logml_grad_tile_supports(n)
+                             ? launch_logml_grad_tile<T>(n, nparam, B, c, d, dM, grad, gradc, alpha, batch, dInfo, stream)
+                             : launch_logml_grad_global<T>(n, nparam, B, c, d, dM, grad, gradc, alpha, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "logml_grad launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int logml_grad_host(int n, int nparam, const void *hBs, const void *hCs, const void *hDs, const void *hDMs, void *hGrad, void *hGradC,
+                    void *hAlpha, size_t batch, int *info)
+{
+    const size_t vec = (size_t)n * batch, mat = vec * n, par = batch * (size_t)nparam;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dDM = nullptr, *dGrad = nullptr, *dGradC = nullptr, *dAlpha = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
+    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dDM), par * (size_t)n * n * sizeof(T));
+    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dGrad), par * sizeof(T));
+    if (e == hipSuccess && hGradC) e = staging_alloc(reinterpret_cast<void **>(&dGradC), vec * sizeof(T));
+    if (e == hipSuccess && hAlpha) e = staging_alloc(reinterpret_cast<void **>(&dAlpha), vec * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hGrad) e = hipMemcpy(dDM, hDMs, par * (size_t)n * n * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = logml_grad_dispatch<T>(n, nparam, dB, dC, dD, dDM, dGrad, dGradC, dAlpha, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hGrad) e = hipMemcpy(hGrad, dGrad, par * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hGradC) e = hipMemcpy(hGradC, dGradC, vec * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hAlpha) e = hipMemcpy(hAlpha, dAlpha, vec * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dDM), staging_free(dGrad), staging_free(dGradC), staging_free(dAlpha);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "logml_grad host<->device");
+    return MATINV_OK;
+}
+
 template <class T>
 int lu_kernel(int n)
 {
@@ -1259,6 +1326,31 @@ int matinv_loo_batched_host(int dtype, int n, const void *hBs, const void *hCs, 
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return loo_host<double>(n, hBs, hCs, hDs, hMean, hVar, hLogPL, batch, info);
     return loo_host<float>(n, hBs, hCs, hDs, hMean, hVar, hLogPL, batch, info);
+}
+
+int matinv_logml_grad_batched(int dtype, int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad,
+                              void *dGradC, void *dAlpha, size_t batch, int *dInfo, void *stream)
+{
+    int rc = logml_grad_check_args(dtype, n, nparam, dBs, dDs, dDMs, dGrad, dGradC, dAlpha, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return logml_grad_dispatch<double>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dAlpha, batch, dInfo, st);
+    return logml_grad_dispatch<float>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dAlpha, batch, dInfo, st);
+}
+
+const char *matinv_logml_grad_kernel_name(int dtype, int n)
+{
+    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return logml_grad_tile_supports(n) ? name_logml_grad_tile(dtype == MATINV_F64, n) : name_logml_grad_global(dtype == MATINV_F64);
+}
+
+int matinv_logml_grad_batched_host(int dtype, int n, int nparam, const void *hBs, const void *hCs, const void *hDs, const void *hDMs,
+                                   void *hGrad, void *hGradC, void *hAlpha, size_t batch, int *info)
+{
+    int rc = logml_grad_check_args(dtype, n, nparam, hBs, hDs, hDMs, hGrad, hGradC, hAlpha, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return logml_grad_host<double>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hAlpha, batch, info);
+    return logml_grad_host<float>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hAlpha, batch, info);
 }
 
 int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dDs,

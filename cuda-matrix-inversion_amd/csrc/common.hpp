@@ -352,6 +352,20 @@ hipError_t launch_loo_global(int n, const T *Bs, const T *Cs, const T *Ds, T *me
                              hipStream_t stream);
 const char *name_loo_global(bool f64);
 
+// Gradients of the batched GP log marginal likelihood (matinv_logml_grad_batched): grad: batch * nparam, gradc, alpha: batch * n, each
+// optional; dMs: batch * nparam symmetric n x n matrices (lower triangle read), needed with grad only.
+// (a) the gradient form of the one-wavefront SPD sweep, n <= 96 (logml_grad_tile_kernels.hip, logml_grad_tile_f32_kernels.hip)
+bool logml_grad_tile_supports(int n);
+template <class T>
+hipError_t launch_logml_grad_tile(int n, int nparam, const T *Bs, const T *Cs, const T *Ds, const T *dMs, T *grad, T *gradc, T *alpha,
+                                  size_t batch, int *info, hipStream_t stream);
+const char *name_logml_grad_tile(bool f64, int n);
+// (b) the gradient form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_logml_grad_global(int n, int nparam, const T *Bs, const T *Cs, const T *Ds, const T *dMs, T *grad, T *gradc, T *alpha,
+                                    size_t batch, int *info, hipStream_t stream);
+const char *name_logml_grad_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

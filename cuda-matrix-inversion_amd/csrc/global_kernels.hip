@@ -346,4 +346,147 @@ template hipError_t launch_loo_global<float>(int, const float *, const float *, 
 
 const char *name_loo_global(bool f64) { return f64 ? "matinv_chol_global<double, true>" : "matinv_chol_global<float, true>"; }
 
+// ---- gradients of the GP log marginal likelihood, 96 < n <= 1024 (matinv_logml_grad_batched behind logml_grad_tile_impl.hpp) ----------
+// The gradient form of matinv_chol_global: one more template argument again ("Gradients of the log marginal likelihood").
+// M = B + diag c is factored in a working copy in library scratch and the factor inverted in place, as above; then
+//     alpha = L^-T (L^-1 d)                                     (the two triangular products of the LOO form, while L^-1 is still there)
+//     K_rc  = sum_{k >= r} (L^-1)_kr (L^-1)_kc,  r >= c         (the lower triangle of M^-1 over L^-1, one column at a time through LDS)
+//     gradc_i = 1/2 (alpha_i^2 - K_ii),   grad_p = sum_{r >= c} w_rc (alpha_r alpha_c - K_rc) dM_p[r][c],  w = 1/2 on the diagonal, 1 below
+// with dM_p read from caller memory (lower triangle only) and grad_p summed per thread in element order, then on a fixed LDS tree.
+// Not SPD: info = the failing column + 1 and every output NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves
+// matrix first + blockIdx.x.
+template <class T, bool LOO, bool GRAD>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Ds, const T *dMs, int nparam, T *grad,
+                                                                 T *gradc, T *alpha, int *info, int n, T *workspace, size_t first)
+{
+    static_assert(LOO && GRAD, "the three-argument form is the log-marginal-likelihood gradient kernel");
+    __shared__ T col[1024], va[1024], vy[1024];
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    T *W = workspace + (size_t)blockIdx.x * n * n;
+    const int t = threadIdx.x;
+    const size_t nn = (size_t)n * n;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    for (int i = t; i < n; i += GL_THREADS) va[i] = Ds[k_mat * n + i];
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        for (int i = t; i < n; i += GL_THREADS) {
+            if (alpha) alpha[k_mat * n + i] = nan_of<T>();
+            if (gradc) gradc[k_mat * n + i] = nan_of<T>();
+        }
+        if (grad)
+            for (int p = t; p < nparam; p += GL_THREADS) grad[k_mat * nparam + p] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+        const T ajj = (T)1 / W[(size_t)j * n + j];
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+        __syncthreads();
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+            W[(size_t)j * n + i] = -s * ajj;
+        }
+        if (t == 0) W[(size_t)j * n + j] = ajj;
+        __syncthreads();
+    }
+    // y = L^-1 d: (L^-1)_kj sits at W[j*n + k]
+    for (int k = t; k < n; k += GL_THREADS) {
+        T s = 0;
+        for (int j = 0; j <= k; ++j) s += W[(size_t)j * n + k] * va[j];
+        vy[k] = s;
+    }
+    __syncthreads();
+    // alpha_i = column i of L^-1 against y; it takes the place of d
+    for (int i = t; i < n; i += GL_THREADS) {
+        T a = 0;
+        for (int k = i; k < n; ++k) a += W[(size_t)i * n + k] * vy[k];
+        va[i] = a;
+        if (alpha) alpha[k_mat * n + i] = a;
+    }
+    __syncthreads();
+    // column c of K over column c of L^-1; the columns beyond c are still those of L^-1
+    for (int c = 0; c < n; ++c) {
+        for (int k = c + t; k < n; k += GL_THREADS) col[k] = W[(size_t)c * n + k];
+        __syncthreads();
+        for (int r = c + t; r < n; r += GL_THREADS) {
+            T s = 0;
+            if (r == c) {
+                for (int k = r; k < n; ++k) s += col[k] * col[k];
+            } else {
+                for (int k = r; k < n; ++k) s += W[(size_t)r * n + k] * col[k];
+            }
+            W[(size_t)c * n + r] = s;
+        }
+        __syncthreads();
+    }
+    if (gradc)
+        for (int i = t; i < n; i += GL_THREADS) gradc[k_mat * n + i] = (T)0.5 * (va[i] * va[i] - W[(size_t)i * n + i]);
+    if (grad) {
+        for (int p = 0; p < nparam; ++p) {
+            const T *D = dMs + (k_mat * nparam + p) * nn;
+            T s = 0;
+            for (size_t e = t; e < nn; e += GL_THREADS) {
+                const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+                if (r < c) continue;
+                const T g = va[r] * va[c] - W[e];
+                s += (r == c ? (T)0.5 : (T)1) * g * D[e];
+            }
+            // block sum on a fixed tree
+            col[t] = s;
+            __syncthreads();
+            for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+                if (t < off) col[t] += col[t + off];
+                __syncthreads();
+            }
+            if (t == 0) grad[k_mat * nparam + p] = col[0];
+            __syncthreads();
+        }
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_logml_grad_global(int n, int nparam, const T *Bs, const T *Cs, const T *Ds, const T *dMs, T *grad, T *gradc, T *alpha,
+                                    size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_loo_global)
+    const size_t mat = (size_t)n * n;
+    size_t chunk = blocked_workspace_cap() / (mat * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * mat * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Bs, Cs, Ds, dMs, nparam, grad,
+                           gradc, alpha, info, n, ws, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_logml_grad_global<double>(int, int, const double *, const double *, const double *, const double *, double *, double *,
+                                                     double *, size_t, int *, hipStream_t);
+template hipError_t launch_logml_grad_global<float>(int, int, const float *, const float *, const float *, const float *, float *, float *,
+                                                    float *, size_t, int *, hipStream_t);
+
+const char *name_logml_grad_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true>" : "matinv_chol_global<float, true, true>";
+}
+
 }  // namespace matinv

@@ -1,0 +1,10 @@
+// logml_grad_tile_f32_kernels.hip -- fp32 instantiation of the one-wavefront log-marginal-likelihood gradient tile kernels
+// (logml_grad_tile_impl.hpp); a translation unit of its own so that the two precisions compile in parallel
+#include "logml_grad_tile_impl.hpp"
+
+namespace matinv {
+
+template hipError_t launch_logml_grad_tile<float>(int, int, const float *, const float *, const float *, const float *, float *, float *, float *,
+                                                  size_t, int *, hipStream_t);
+
+}  // namespace matinv

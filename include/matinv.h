@@ -215,6 +215,28 @@ const char *matinv_loo_kernel_name(int dtype, int n);
 int matinv_loo_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hMean, void *hVar, void *hLogPL,
                             size_t batch, int *info);
 
+/* Gradients of the GP log marginal likelihood (the one matinv_logml_batched returns), device-resident. With M_k = B_k + diag(c_k),
+ * K = M^-1, alpha = K d and nparam symmetric derivative matrices dM_p = dM / d theta_p per matrix:
+ *   grad[k*nparam + p] = 1/2 sum_ij (alpha_i alpha_j - K_ij) dM_p[i][j]      d logml / d theta_p = 1/2 tr((alpha alpha^T - K) dM_p)
+ *   gradc[k*n + i]     = 1/2 (alpha_i^2 - K_ii)                              d logml / d c_i
+ *   alpha[k*n + i]     = alpha_i                                             what the predictive mean needs
+ * B, c, d as in matinv_loo_batched (SPD, column-major, only the lower triangle read; dCs may be NULL). dDMs: batch*nparam*n*n elements,
+ * matrix (k, p) at offset (k*nparam + p)*n*n, column-major; only its lower triangle is read, the upper one is implied by symmetry.
+ * dGrad: batch*nparam, dGradC, dAlpha: batch*n; each may be NULL (all three NULL: MATINV_ERR_ARG), and which of them are requested
+ * does not change a bit of the others. dGrad needs nparam >= 1 and dDMs; without dGrad, nparam = 0 and dDMs = NULL are fine (dDMs is
+ * not read). No input is modified (outputs must not overlap inputs); neither M nor its inverse is written to caller memory; the result
+ * of matrix k depends on matrix k alone. dInfo (optional): 0, or the 1-based column of the first non-positive (or NaN) pivot -- every
+ * output of that matrix is then NaN. n <= 96: the gradient form of the one-wavefront SPD tile sweep ((nparam + 1) n^2/2 + 2n elements
+ * read, nparam + 2n written). Beyond, to n = 1024: the gradient form of the global-memory Cholesky kernel on a working copy in library
+ * scratch. The log marginal likelihood itself is not an output here. Asynchronous, no host synchronisation. */
+int matinv_logml_grad_batched(int dtype, int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad,
+                              void *dGradC, void *dAlpha, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a gradient request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_logml_grad_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional; hDMs is read only with hGrad). Synchronous. */
+int matinv_logml_grad_batched_host(int dtype, int n, int nparam, const void *hBs, const void *hCs, const void *hDs, const void *hDMs,
+                                   void *hGrad, void *hGradC, void *hAlpha, size_t batch, int *info);
+
 /* Host-pointer convenience used by the reference-named *_gpu wrappers: allocate, H2D, invert, D2H, free.
  * `info` is an optional host int[batch]. Synchronous. */
 int matinv_inverse_batched_host(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info);
