@@ -124,7 +124,7 @@ __global__ __launch_bounds__(BGP_THREADS) void matinv_bgp_panel(T *W, int n, int
         if (c < pb) w[(size_t)(k0 + c) * ld + r] = x[c];
 }
 
-// trailing update: W[I, J] -= L[I, K] L[J, K]^T for 64 x 64 tiles with jbeg <= J < jend, I >= J (rows up to row_end - 1);
+// trailing update: W[I, J] -= L[I, K] L[J, K]^T (accumulated onto W, column by column) for 64 x 64 tiles with jbeg <= J < jend, I >= J (rows up to row_end - 1);
 // K = the kcnt panel columns from kbeg on (one panel of 64, or the two panels of a pair: see launch_gp_blocked)
 // LDL = true (the block-LDL^T path below): the J side of the product is read from the raw copy of the panel in Sraw (per item
 // BGP_PB columns of leading dimension ld, same row index as the working copy) instead of from the working copy itself.
@@ -146,7 +146,22 @@ __global__ __launch_bounds__(BGP_THREADS, MATINV_BGP_OCC) void matinv_bgp_update
     const int t = threadIdx.x, wv = t >> 6, q = (t >> 4) & 3, c = t & 15;
     // this wavefront's 32 x 32 part strictly above the diagonal: it only helps staging (wave-uniform)
     const bool live = i0 + 32 * (wv & 1) + 32 > j0 + 32 * (wv >> 1);
+    // The accumulators START from the tile and the I side is staged negated, so every panel column is one more link of the same chain
+    // W - l_0 l_0^T - l_1 l_1^T - ...: the rank-128 update of a panel pair then rounds exactly as the two rank-64 updates it replaces
+    // (a store and a load between them change nothing), and whether panels are paired -- decided from the batch size, bgp_pairs_pay --
+    // does not show in the result: a matrix's bits depend on that matrix alone (include/matinv.h).
     typename G::vec4 acc[2][2] = {};
+    if (live) {
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+            for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int J = j0 + 32 * (wv >> 1) + 16 * tj + G::trow(r, q), I = i0 + 32 * (wv & 1) + 16 * ti + c;
+                    if (I < row_end && J < jend && I >= J) acc[tj][ti][r] = w[(size_t)J * ld + I];
+                }
+    }
     // slabs of BGP_KS panel columns through LDS; the NEXT slab is fetched into registers while the current one is multiplied
     // (thread t fetches row t & 63 of columns (t >> 6) + 4 x; clamped addresses, so the loads are unconditional). Fetching TWO
     // slabs ahead was measured and lost: 130 VGPRs, three waves per SIMD instead of four, 1024^2 fp64 SPD inverse 23.7 ms against 21.4.
@@ -171,7 +186,7 @@ __global__ __launch_bounds__(BGP_THREADS, MATINV_BGP_OCC) void matinv_bgp_update
 #pragma unroll
         for (int x = 0; x < BGP_KS / 4; ++x) {
             const bool kin = ks + lk + 4 * x < pb;
-            Li[lk + 4 * x][lr] = (kin && in_i) ? pi[x] : (T)0;
+            Li[lk + 4 * x][lr] = (kin && in_i) ? -pi[x] : (T)0;
             Lj[lk + 4 * x][lr] = (kin && in_j) ? pj[x] : (T)0;
         }
         __syncthreads();
@@ -186,7 +201,7 @@ __global__ __launch_bounds__(BGP_THREADS, MATINV_BGP_OCC) void matinv_bgp_update
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int J = j0 + 32 * (wv >> 1) + 16 * tj + G::trow(r, q), I = i0 + 32 * (wv & 1) + 16 * ti + c;
-                if (I < row_end && J < jend && I >= J) w[(size_t)J * ld + I] -= acc[tj][ti][r];
+                if (I < row_end && J < jend && I >= J) w[(size_t)J * ld + I] = acc[tj][ti][r];
             }
 }
 
@@ -332,6 +347,12 @@ __global__ __launch_bounds__(BGP_THREADS, 2) void matinv_bldl_panel(T *W, T *Sra
     if (wv == 0) {  // wave-uniform
         int binfo = 0;
         spd_invert64_wave<T>(Sd, LD, Gs, LD, panel, t, binfo);
+        if constexpr (sizeof(T) == 4) {
+            if (binfo != 0) {  // the fp32 tile order does not say which column fails FIRST (tile_common.hpp); Sd is not needed again
+                const int nat = spd_natural_first_failure_lds<T>(Sd, LD, BGP_PB, t);
+                if (nat) binfo = nat;
+            }
+        }
         if (t == 0) sh_bad = binfo;
     }
     __syncthreads();

@@ -159,7 +159,14 @@ __device__ __forceinline__ void logdet_tile_body(const T *As, size_t stride, con
             out0[mat] = ok ? ld : nan_of<T>();
             if (out1) out1[mat] = ok ? (T)1 : nan_of<T>();
         }
-        if (info && l == 0) info[mat] = binfo;
+        int code = binfo;
+        if constexpr (sizeof(T) == 4) {
+            if (bad != 0) {  // wave-uniform; rejected matrices only: the fp32 tile order does not say which column fails FIRST (tile_common.hpp)
+                const int nat = spd_natural_first_failure<NT, T>(A, (BORDER && Cs) ? Cs + (size_t)mat * n : nullptr, n, panel, l);
+                if (nat) code = nat;
+            }
+        }
+        if (info && l == 0) info[mat] = code;
         wave_lds_sync();
     }
 }

@@ -263,7 +263,14 @@ __device__ __forceinline__ void logml_grad_tile_body(const T *Bs, const T *Cs, c
                 if (l == 0) grad[(size_t)mat * nparam + p] = ok ? s : nan_of<T>();
             }
         }
-        if (l == 0 && info) info[mat] = binfo;
+        int code = binfo;
+        if constexpr (sizeof(T) == 4) {
+            if (bad != 0) {  // wave-uniform; rejected matrices only: the fp32 tile order does not say which column fails FIRST (tile_common.hpp)
+                const int nat = spd_natural_first_failure<NT, T>(A, Cs ? Cs + (size_t)mat * n : nullptr, n, panel, l);
+                if (nat) code = nat;
+            }
+        }
+        if (l == 0 && info) info[mat] = code;
         wave_lds_sync();  // the next matrix's first panel write must not pass this one's last reads
     }
 }

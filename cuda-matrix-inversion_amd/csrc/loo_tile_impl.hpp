@@ -211,10 +211,21 @@ __device__ __forceinline__ void loo_tile_body(const T *Bs, const T *Cs, const T 
             if (logpl) logpl[mat] = ok ? term - (T)n * (T)0.91893853320467274178 : nan_of<T>();
             if (info) info[mat] = binfo;
         }
+        if constexpr (sizeof(T) == 4) {
+            // Rejected matrices only (wave-uniform): the fp32 tile order does not say which column fails FIRST (tile_common.hpp), so info
+            // is written once more, in a block of its own after the stores.
+            if (bad != 0 && info) {
+                const int nat = spd_natural_first_failure<NT, T>(Bs + (size_t)mat * n * n, Cs ? Cs + (size_t)mat * n : nullptr, n, panel, l);
+                if (nat && l == 0) info[mat] = nat;
+            }
+        }
         wave_lds_sync();  // the next matrix's first panel write must not pass this one's last reads
     }
 }
 
+// fp32, 4 x 4 tiles: built for FIVE waves per SIMD, which is what its 94 / 96 registers gave it under the bound of four -- with the
+// natural-order pass behind the sweep the ragged form came out at 97 registers (104 allocated: four waves) under that bound, inlined
+// or not, wherever the pass was placed; under the bound of five it is 96 again, without scratch (profiles/loo_kernel_registers.txt).
 // The LOO forms of matinv_spd_tile_f64 / matinv_spd_tile_f32 (tile_impl.hpp): the same names with a third template argument, the
 // same launch bounds for the same NT -- except the two fp64 ragged forms that spill under them (3 x 3 tiles at four waves per SIMD: 2
 // registers, 6 x 6 at two: 8; profiles/loo_kernel_registers.txt), which take one wave less per SIMD and no scratch.
@@ -234,7 +245,7 @@ __global__ __launch_bounds__(64, loo_f64_waves(NT, FULL)) void matinv_spd_tile_f
 }
 
 template <int NT, bool FULL, bool LOO>
-__global__ __launch_bounds__(64, NT >= 5 ? 3 : 4) void matinv_spd_tile_f32(const float *Bs, const float *Cs, const float *Ds, float *mean,
+__global__ __launch_bounds__(64, NT >= 5 ? 3 : (NT == 4 ? 5 : 4)) void matinv_spd_tile_f32(const float *Bs, const float *Cs, const float *Ds, float *mean,
                                                                           float *var, float *logpl, int *info, int n_rt, unsigned batch)
 {
     static_assert(LOO, "the three-argument form is the leave-one-out kernel");

@@ -311,7 +311,12 @@ __global__ __launch_bounds__(ROWLANE_THREADS, rowlane_occupancy(sizeof(T), NP, F
             T negm = (i == k) ? (T)0 : -(a[k] * inv);
             if (SPD && !(piv > 0) && bad == 0) bad = k + 1;  // not positive definite (NaN included)
             const bool viol = !SPD && !(absval(negm) <= (T)ROWLANE_TAU);
-            if (!SPD && __any(viol)) {
+            const unsigned long long viols = SPD ? 0ull : __ballot(viol);
+            if (!SPD && viols != 0ull) {
+                // The branch is wave-wide, the search is not: only a matrix one of whose OWN multipliers failed the test gives up its
+                // diagonal pivot. (Until every matrix of the wave searched once one of them had to, the bits of a matrix depended on
+                // the 3 or 7 matrices it shared a wavefront with: include/matinv.h promises they depend on that matrix alone.)
+                const bool mine = ((unsigned)(viols >> (g * NP)) & ((1u << NP) - 1u)) != 0u;
                 // pivot search in column k over rows >= k of this lane's matrix
                 const unsigned key = (i >= k) ? mag_key(a[k]) : 0u;
                 const unsigned mx = group_max<NP>(key);
@@ -319,9 +324,9 @@ __global__ __launch_bounds__(ROWLANE_THREADS, rowlane_occupancy(sizeof(T), NP, F
                 const unsigned long long vote = __ballot(is_max);
                 const unsigned gbits = (unsigned)(vote >> (g * NP)) & ((1u << NP) - 1u);
                 const int p = __builtin_ctz(gbits | 0x80000000u);  // lowest row attaining the maximum
-                const bool singular = (mx == 0u) || key_not_finite(T(0), mx);
+                const bool singular = mine && ((mx == 0u) || key_not_finite(T(0), mx));
                 if (singular && bad == 0) bad = k + 1;
-                const bool need_swap = (p != k) && !singular;
+                const bool need_swap = mine && (p != k) && !singular;
                 if (__any(need_swap)) {
                     any_swap = true;
                     const int partner = need_swap ? ((i == k) ? p : (i == p) ? k : i) : i;

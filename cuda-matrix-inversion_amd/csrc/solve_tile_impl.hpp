@@ -229,7 +229,14 @@ __device__ __forceinline__ void solve_tile_body(BatchRef<const T> Ain, BatchRef<
                         if (z < nrhs && (FULL || col < n)) X[(unsigned)(z * n + col)] = sgn * zacc[tj][r];
                     }
             }
-            if (info && l == 0) info[mat] = SPD ? binfo : 0;
+            int code = SPD ? binfo : 0;
+            if constexpr (SPD && sizeof(T) == 4) {
+                if (bad != 0) {  // wave-uniform; rejected matrices only: the fp32 tile order does not say which column fails FIRST (tile_common.hpp)
+                    const int nat = spd_natural_first_failure<NT, T>(A, (const T *)nullptr, n, panel, l);
+                    if (nat) code = nat;
+                }
+            }
+            if (info && l == 0) info[mat] = code;
         } else if (l == 0) {
             const int slot = atomicAdd(work_count, 1);
             work_list[slot] = (int)mat;

@@ -19,7 +19,9 @@ constexpr int TILE_TSTRIDE = 17;  // padded row stride of the 16 x 16 LDS transp
 // groups q = 0..3 (that is what makes the B operand free), and its 4 columns must carry the same tile-local indices:
 //   f64: block b = rows/cols 4b .. 4b+3          (lane c belongs to block c>>2, is pivot number c&3)
 //   f32: block b = rows/cols b, b+4, b+8, b+12   (lane c belongs to block c&3,  is pivot number c>>2)
-// i.e. the f32 kernels eliminate in a permuted order -- a symmetric relabelling, invisible in the result.
+// i.e. the f32 kernels eliminate in a permuted order -- a symmetric relabelling, invisible in the result, but not in WHICH pivot
+// is the first to fail: an f32 kernel that reports through PanelSolve::binfo names a column of the right 16-column tile (every
+// earlier tile passed in either order), not necessarily the first non-positive leading minor (include/matinv.h, dInfo).
 template <class T>
 struct TileGeo;
 template <>
@@ -153,6 +155,102 @@ __device__ __forceinline__ void note_nonpositive_first(unsigned long long &bad, 
                  : "vcc", "scc");
 }
 
+// ---- error path of the fp32 kernels that write info themselves ---------------------------------------------------------------------
+// The fp32 sweeps eliminate the 16 columns of a tile in the order of TileGeo<float>::pcol, so the first pivot they see fail lies in the
+// right tile but is not necessarily the first non-positive leading minor, which is what info has to name (include/matinv.h). A matrix
+// that failed is therefore factorised once more in NATURAL order, one column at a time (rank-1 LDL^T steps, no blocking), until the
+// first non-positive (or NaN) pivot shows. Only rejected matrices come here: the sweep itself is what it was.
+// Returns the 1-based column, or 0 when every natural-order pivot was positive (a borderline matrix that only the rounding of the
+// permuted order rejects: the caller keeps the sweep's own code).
+//
+// One wavefront, matrix re-read from memory (lower triangle of the column-major n x n block at A, leading dimension n; cdiag: optional
+// vector added to the diagonal) into lower accumulator tiles -- the sweep's own are dead by now. colbuf: 16 NT elements of LDS.
+template <int NT, class T>
+__device__ __forceinline__ int spd_natural_first_failure(const T *A, const T *cdiag, int n, T *colbuf, int l)
+{
+    typedef TileGeo<T> G;
+    typedef typename G::vec4 vec4;
+    int q = l >> 4, c = l & 15;
+    asm volatile("" : "+v"(q), "+v"(c));
+    vec4 w[NT][NT];
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < NT; ++tj) {
+            if (tj > ti) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = 16 * ti + G::trow(r, q), col = 16 * tj + c;
+                const bool in = row < n && col < n;
+                const int hi = row > col ? row : col, lo = row > col ? col : row;
+                T v = in ? A[(unsigned)(lo * n + hi)] : ((row == col) ? (T)1 : (T)0);
+                if (cdiag && ti == tj && row == col && in) v += cdiag[row];
+                w[ti][tj][r] = v;
+            }
+        }
+    int found = 0;
+#pragma unroll
+    for (int tj = 0; tj < NT; ++tj) {
+#pragma nounroll
+        for (int jj = 0; jj < 16; ++jj) {
+            const int j = 16 * tj + jj;
+            if (found != 0 || j >= n) break;
+            // column j, rows from its tile on: the lanes with c == jj hold it (diagonal tiles are complete)
+            wave_lds_sync();
+            if (c == jj) {
+#pragma unroll
+                for (int ti = tj; ti < NT; ++ti)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) colbuf[16 * ti + G::trow(r, q)] = w[ti][tj][r];
+            }
+            wave_lds_sync();
+            const T piv = colbuf[j];
+            if (__ballot(!(piv > (T)0)) != 0ull) {  // every lane read the same element
+                found = j + 1;
+                break;
+            }
+            const T rp = (T)1 / piv;
+            // rows and columns already eliminated keep rounding residue only; it never reaches a live element
+#pragma unroll
+            for (int tk = tj; tk < NT; ++tk) {
+                const T wc = colbuf[16 * tk + c] * rp;
+#pragma unroll
+                for (int ti = tk; ti < NT; ++ti)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) w[ti][tk][r] = fma_t(-colbuf[16 * ti + G::trow(r, q)], wc, w[ti][tk][r]);
+            }
+        }
+    }
+    wave_lds_sync();
+    return found;
+}
+
+// The same for one wavefront on a block in LDS: S, m x m, column-major with leading dimension ld, lower triangle; destroyed.
+template <class T>
+__device__ __forceinline__ int spd_natural_first_failure_lds(T *S, int ld, int m, int l)
+{
+    int found = 0;
+    for (int j = 0; j < m && found == 0; ++j) {
+        wave_lds_sync();
+        const T piv = S[j * ld + j];
+        if (__ballot(!(piv > (T)0)) != 0ull) {
+            found = j + 1;
+        } else {
+            const T rp = (T)1 / piv;
+            const int k = m - j - 1;
+            for (int e = l; e < k * k; e += 64) {
+                const int cc = e / k, rr = e - cc * k;
+                if (rr >= cc) {
+                    const int C = j + 1 + cc, R = j + 1 + rr;
+                    S[C * ld + R] = fma_t(-S[j * ld + R], S[j * ld + C] * rp, S[C * ld + R]);
+                }
+            }
+        }
+    }
+    wave_lds_sync();
+    return found;
+}
+
 // SPD = true: symmetric blocked sweep for SPD input (see matinv_spd_tile_f64). Same arithmetic for D^-1 and Aop; the
 // acceptance test becomes "all four pivots of D positive" (they are the squares of the Cholesky diagonal), and the
 // stage of tile row ti also returns bsym[ti] = P[16ti + c][q], the B operand by symmetry (W[K, J] = W[J, K]^T).
@@ -171,7 +269,7 @@ template <int NT, bool SPD = false, class T = double, bool GATED = false, bool B
 struct PanelSolve {
     typedef TileGeo<T> G;
     static constexpr int NSTAGE = 6 + NT;
-    int *binfo = nullptr;  // SPD: when set, *binfo becomes (column of the FIRST non-positive pivot) + 1 (scalar selects only)
+    int *binfo = nullptr;  // SPD: when set, *binfo becomes (column of the FIRST non-positive pivot in elimination order) + 1 (scalar selects only)
     T d[4][4];
     T r0, r1, r2, r3, l10, l20, l30, l21, l31, l32, u11, u12, u13, u22, u23, u33;
     T a21, a22, a23, a31, a32, a33, b32, b33, y0, y1, y2, y3, x0, x1, x2, x3;

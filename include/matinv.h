@@ -98,6 +98,12 @@ int matinv_set_gj_policy(int policy); /* returns the previous policy, or MATINV_
  *                every kernel reads a whole matrix before writing it); partial overlap is undefined.
  *   dInfo   out: optional int[batch] (device). 0 = ok; k+1 = no usable pivot at elimination step k
  *                (Gauss-Jordan: singular) or leading minor k+1 not positive (Cholesky: not SPD).
+ *                Gauss-Jordan: for a matrix with several deficient columns the code names one of them, not necessarily the first.
+ *                Cholesky, MATINV_F32, 160 < n <= 256 under MATINV_KERNEL_AUTO or MATINV_KERNEL_TILE (and the solve composed from
+ *                that inversion): the kernel eliminates the 16 columns of a tile in a permuted order, and the code names a column of
+ *                the same 16-column tile [16 t, 16 t + 16) as the first non-positive leading minor, never one beyond n. It is that
+ *                column itself when a single non-positive diagonal entry is all that keeps the matrix from being positive
+ *                definite. Every other path, in both dtypes, names the column itself.
  *                For info != 0 the output matrix is filled with NaN (never left half-written).
  *   stream     : hipStream_t as void* (NULL = default stream). Asynchronous.
  */
