@@ -34,7 +34,7 @@ NATIVE_NAMES = [
     "matinv_mean_batched", "matinv_variance_batched", "matinv_inverse_batched_host", "matinv_mean_batched_host",
     "matinv_variance_batched_host", "matinv_last_error",
     "matinv_abi_version", "matinv_release_cache", "matinv_stream_retire", "matinv_batched_malloc", "matinv_batched_free", "matinv_memcpy_2d",
-    "matinv_device_synchronize", "matinv_tile_stats", "matinv_queue_create", "matinv_queue_submit", "matinv_queue_submit_chunks", "matinv_queue_pending",
+    "matinv_device_synchronize", "matinv_tile_stats", "matinv_sym_front_stats", "matinv_queue_create", "matinv_queue_submit", "matinv_queue_submit_chunks", "matinv_queue_pending",
     "matinv_queue_bins", "matinv_queue_flush", "matinv_queue_destroy", "matinv_queue_last_error", "matinv_queue_stream",
     "matinv_set_gj_policy", "matinv_device_count", "matinv_shard_range", "matinv_inverse_batched_host_multi", "matinv_comm_unique_id",
     "matinv_comm_init_rank", "matinv_comm_destroy", "matinv_allgather_shards", "matinv_allgather_local", "matinv_allgather_local_after", "matinv_debug_rejects",
@@ -147,6 +147,9 @@ def lib() -> ctypes.CDLL:
     L.matinv_allgather_local_after.argtypes = [ci, vp, ci, vp, vp, sz, vp]
     L.matinv_tile_stats.restype = ci
     L.matinv_tile_stats.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "matinv_sym_front_stats"):  # an older library selected with MATINV_LIB (A/B runs) does not have it
+        L.matinv_sym_front_stats.restype = ci
+        L.matinv_sym_front_stats.argtypes = [vp, vp, vp, vp]
     L.matinv_batched_malloc.restype = ci
     L.matinv_batched_malloc.argtypes = [vp, vp, sz, ci]
     L.matinv_batched_free.restype = ci

@@ -530,6 +530,14 @@ def tile_stats() -> dict:
     return dict(zip(("natural_launches", "pivot_launches", "last_rejected", "last_batch"), (int(x.value) for x in v)))
 
 
+def sym_front_stats() -> dict:
+    """matinv_sym_front_stats: which route the unscreened 64 x 64 fp64 Gauss-Jordan launches took since load (symmetric-only kernel in
+    front / two-arm kernel alone) and what the last completed front launch found."""
+    v = [ctypes.c_ulonglong(0) for _ in range(4)]
+    _lib.check(_lib.lib().matinv_sym_front_stats(*[ctypes.byref(x) for x in v]))
+    return dict(zip(("front_launches", "direct_launches", "last_not_symmetric", "last_batch"), (int(x.value) for x in v)))
+
+
 def select_kernel(algo: int, dtype, n: int) -> int:
     code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
     k = _lib.lib().matinv_select_kernel(algo, code, n)

@@ -1133,6 +1133,18 @@ int matinv_tile_stats(unsigned long long *natural_launches, unsigned long long *
     return MATINV_OK;
 }
 
+// which route the unscreened 64 x 64 fp64 Gauss-Jordan launches took (tile_kernels.hip "symmetric-only kernel in front")
+int matinv_sym_front_stats(unsigned long long *front_launches, unsigned long long *direct_launches, unsigned long long *last_not_symmetric,
+                           unsigned long long *last_batch)
+{
+    const SymFrontStats s = sym_front_stats();
+    if (front_launches) *front_launches = s.front_launches;
+    if (direct_launches) *direct_launches = s.direct_launches;
+    if (last_not_symmetric) *last_not_symmetric = s.last_not_symmetric;
+    if (last_batch) *last_batch = s.last_batch;
+    return MATINV_OK;
+}
+
 int matinv_device_synchronize(void)
 {
     hipError_t e = hipDeviceSynchronize();

@@ -227,7 +227,8 @@ hipError_t launch_gj_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_t bat
 // (bad_count, bad_list), zeroed by the caller; hint_out (pinned host memory, may be null) receives the list length
 template <class T>
 hipError_t launch_gj_tilep_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count, const int *in_list,
-                                    int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many = false);
+                                    int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many = false,
+                                    const int *aux_count = nullptr, hint_t *aux_out = nullptr);
 const char *name_gj_tilep(bool f64, int n);
 // four wavefronts per matrix, 64 < n <= 128 (tilep4_kernels.hip)
 template <class T>
@@ -251,6 +252,12 @@ struct TileStats {
 };
 TileStats tile_stats();
 bool tile_policy_use_pivot(bool f64, int nt);
+// 64 x 64 fp64: launches that ran the symmetric-only kernel in front / the two-arm kernel alone, and what the last completed front
+// launch found (tile_kernels.hip)
+struct SymFrontStats {
+    unsigned long long front_launches, direct_launches, last_not_symmetric, last_batch;
+};
+SymFrontStats sym_front_stats();
 hint_t *tile_policy_record(bool f64, int nt, size_t batch);
 int gj_policy();                // a matinv_gj_policy (include/matinv.h)
 int set_gj_policy(int policy);  // returns the previous one

@@ -61,6 +61,10 @@
 #define MATINV_TILE_SYM_SWEEP 1  // 0: bitwise-symmetric 64 x 64 fp64 input takes the full sweep like any other (A/B builds)
 #endif
 
+#ifndef MATINV_TILE_SYM_FRONT
+#define MATINV_TILE_SYM_FRONT 1  // 0: no symmetric-only kernel in front of the two-arm 64 x 64 fp64 kernel (A/B builds)
+#endif
+
 namespace matinv {
 
 // ---- pieces of one block step ---------------------------------------------------------------------------------
@@ -604,10 +608,95 @@ _Pragma("unroll")                                                               
         } else {
             MATINV_GJ_TILE_LEAVE
         }
-#undef MATINV_GJ_TILE_LEAVE
         if (LOOKAHEAD) wave_lds_sync();  // the next matrix's first panel write must not pass this one's last reads
     }
 }
+
+// ---- the symmetric-only form of the 64 x 64 fp64 kernel (MATINV_TILE_SYM_FRONT) ------------------------------------------------
+// The two-arm kernel above is allocated for its full sweep (222 VGPRs, two waves per SIMD) although a symmetric batch never runs it.
+// This form holds the symmetric arm alone -- the same sym_tile_sweep, sym_tile_finish and store text, hence the same bits -- at three
+// waves per SIMD. A matrix that is not symmetric is not inverted here: its index goes to a list of its own, and the two-arm kernel
+// takes that list as its accept list (launch_gj_tile_natural). Nothing is stored for it and its info is left alone.
+
+// Item k of the classification: the six off-diagonal pairs first (their upper tiles are dead once compared), then the diagonal tiles.
+constexpr int sym_cls_ti(int k) { return k < 6 ? (k < 1 ? 1 : (k < 3 ? 2 : 3)) : k - 6; }
+constexpr int sym_cls_tj(int k) { return k < 6 ? (k < 1 ? 0 : (k < 3 ? k - 1 : k - 3)) : k - 6; }
+
+// The verdict of tile_asymmetry (== 0), CB tiles per LDS round trip and without the early leave: every element against its mirror as
+// 64-bit integers. tbuf: CB padded 16 x 16 transpose buffers.
+template <int CB>
+__device__ __forceinline__ bool tile_symmetric_batched(double *tbuf, const v4d (&acc)[4][4], int q, int c)
+{
+    typedef TileGeo<double> G;
+    constexpr int NITEM = 10, TSZ = 16 * TILE_TSTRIDE;
+    unsigned long long asym = 0;
+#pragma unroll
+    for (int g = 0; g < NITEM; g += CB) {
+        wave_lds_sync();
+#pragma unroll
+        for (int k = g; k < g + CB && k < NITEM; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tbuf[(k - g) * TSZ + G::trow(r, q) * TILE_TSTRIDE + c] = acc[sym_cls_ti(k)][sym_cls_tj(k)][r];
+        wave_lds_sync();
+#pragma unroll
+        for (int k = g; k < g + CB && k < NITEM; ++k)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                note_differs(asym, tbuf[(k - g) * TSZ + c * TILE_TSTRIDE + G::trow(r, q)], acc[sym_cls_tj(k)][sym_cls_ti(k)][r]);
+    }
+    return asym == 0;
+}
+
+constexpr int TILE_SYM_CLS_BATCH = 5;  // tiles per round trip of the classification: two round trips instead of ten, 10 880 B of LDS
+
+__device__ __forceinline__ void gj_tile_sym_body(BatchRef<const double> Ain, BatchRef<double> Xout, int *info, unsigned batch, int *work_count,
+                                                 int *work_list, int *ns_count, int *ns_list, double *panel)
+{
+    typedef double T;
+    typedef TileGeo<T> G;
+    typedef typename G::vec4 vec4;
+    typedef typename G::vec2 vec2;
+    constexpr int NT = 4, N = 16 * NT;
+    constexpr bool FULL = true, PAIRED = true;  // what the store text of gj_tile_body reads
+    const int l = threadIdx.x;
+
+    for (unsigned mat = blockIdx.x; mat < batch; mat += gridDim.x) {
+        const T *A = Ain.at_uniform(mat);
+        T *X = Xout.at_uniform(mat);
+        constexpr int n = N;
+        constexpr unsigned lane_off = 0;  // the store text's other branch only
+        int q = l >> 4, c = l & 15;
+        asm volatile("" : "+v"(q), "+v"(c));  // see gj_tile_body
+        vec4 acc[NT][NT];
+        {
+            const unsigned lane_off2 = (unsigned)(2 * G::trow(0, l >> 4) * N + 2 * (l & 15));
+#pragma unroll
+            for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+                for (int u = 0; u < NT / 2; ++u)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const unsigned uoff = (unsigned)((32 * (ti >> 1) + 2 * G::trow(r, 0) + (ti & 1)) * N + 32 * u);
+                        const vec2 v = __builtin_nontemporal_load(reinterpret_cast<const vec2 *>(A + uoff + lane_off2));
+                        acc[ti][2 * u][r] = v[0];
+                        acc[ti][2 * u + 1][r] = v[1];
+                    }
+        }
+        unsigned long long bad = 0;
+        if (tile_symmetric_batched<TILE_SYM_CLS_BATCH>(panel, acc, q, c)) {
+            wave_lds_sync();  // the transpose buffer becomes the panel
+            sym_tile_sweep<NT, MATINV_TILE_GATED_PANEL != 0, T>(acc, panel, q, c, bad);
+            wave_lds_sync();  // ... and the transpose buffer again
+            if (bad == 0) sym_tile_finish<NT>(panel, acc, q, c);  // wave-uniform; a reject goes to the work list as it is
+            MATINV_GJ_TILE_LEAVE
+        } else if (l == 0) {
+            const int slot = atomicAdd(ns_count, 1);
+            ns_list[slot] = (int)mat;
+        }
+        wave_lds_sync();
+    }
+}
+#undef MATINV_GJ_TILE_LEAVE
 
 
 // FULL: n == 16*NT known at compile time (constant address offsets, no bounds checks).
@@ -624,6 +713,19 @@ __global__ __launch_bounds__(64, 2) void matinv_gj_tile_f64(BatchRef<const doubl
     constexpr bool SYM = MATINV_TILE_SYM_SWEEP && NT == 4 && FULL && LOOKAHEAD;
     __shared__ __attribute__((aligned(16))) double panel[SYM && 16 * NT * 4 < 16 * TILE_TSTRIDE ? 16 * TILE_TSTRIDE : 16 * NT * 4];
     gj_tile_body<double, NT, FULL, LOOKAHEAD, EARLY>(Ain, Xout, info, n_rt, batch, work_count, work_list, panel, in_count, in_list);
+}
+
+// The symmetric-only form (gj_tile_sym_body): an overload with one more, trailing, template argument, so that the kernels above keep
+// their symbols and their code. Instantiated for <4, true, true, false, true> only. 168 VGPRs, no scratch, three waves per SIMD.
+template <int NT, bool FULL, bool LOOKAHEAD, bool EARLY, bool SYMONLY>
+__global__ __launch_bounds__(64, 3) void matinv_gj_tile_f64(BatchRef<const double> Ain, BatchRef<double> Xout, int *info, int n_rt,
+                                                            unsigned batch, int *work_count, int *work_list, int *ns_count, int *ns_list)
+{
+    static_assert(NT == 4 && FULL && LOOKAHEAD && !EARLY && SYMONLY, "the symmetric-only form exists at 64 x 64 only");
+    (void)n_rt;
+    __shared__ __attribute__((aligned(16))) double panel[TILE_SYM_CLS_BATCH * 16 * TILE_TSTRIDE];
+    static_assert(sizeof(panel) >= sizeof(double) * 16 * NT * 4 && 12 * sizeof(panel) <= 160 * 1024, "panel + transpose buffers, 12 workgroups per CU");
+    gj_tile_sym_body(Ain, Xout, info, batch, work_count, work_list, ns_count, ns_list, panel);
 }
 
 // fp32 (the reference's DataType): v_mfma_f32_16x16x4_f32, 4 VGPRs per tile (64 at n = 64), same algorithm; the pivot
@@ -926,7 +1028,15 @@ __global__ __launch_bounds__(64, NT >= 9 ? MATINV_SPD_WIDE_OCC : 2) void matinv_
 // The natural-order pass of the Gauss-Jordan entry point for n <= 64 (default policy): [screen +] verified natural-order kernel, then
 // the pivoting kernel over the matrices they rejected, all in `stream`. ws: [0] rejected, [1] singular, [2] accepted (screened launches),
 // [4 .. 4+batch) rejected matrices, then the singular ones among them, then the accepted ones.
+//
+// 64 x 64 fp64, unscreened (MATINV_TILE_SYM_FRONT): the FRONT route runs the symmetric-only form over the batch and then the two-arm
+// kernel over the matrices that form found not symmetric (ws[3] counts them, their list takes the place of the accepted one: a
+// screened launch never takes the front route), on one round of resident workgroups -- an empty list costs one small launch. The
+// DIRECT route is the two-arm kernel over the batch. Which of them runs is decided by launch history alone
+// (tile_policy_use_sym_front); a matrix gets the same bits either way, since its arm is the same code in both kernels.
 bool tile_policy_use_screen(bool f64, int nt);
+bool tile_policy_use_sym_front(int nt);
+hint_t *tile_policy_record_sym_front(int nt);
 template <class T>
 hipError_t launch_gj_tile_natural(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream)
 {
@@ -934,10 +1044,25 @@ hipError_t launch_gj_tile_natural(int n, BatchRef<const T> A, BatchRef<T> X, siz
     const TileShape s = tile_shape(n);
     const bool rowlane2 = rowlane2_supports(n);
     const bool screen = !rowlane2 && tile_policy_use_screen(F64, s.nt);
-    return with_scratch_ints((screen ? 3 : 2) * batch + 4, 4, stream, [&](int *ws) {
-        int *const rej_count = ws, *const sing_count = ws + 1, *const acc_count = ws + 2;
-        int *const rej_list = ws + 4, *const sing_list = ws + 4 + batch, *const acc_list = ws + 4 + 2 * batch;
+    const bool front = MATINV_TILE_SYM_FRONT && MATINV_TILE_SYM_SWEEP && F64 && n == 64 && !screen && tile_policy_use_sym_front(s.nt);
+    return with_scratch_ints((screen || front ? 3 : 2) * batch + 4, 4, stream, [&](int *ws) {
+        int *const rej_count = ws, *const sing_count = ws + 1, *const acc_count = ws + 2, *const ns_count = ws + 3;
+        int *const rej_list = ws + 4, *const sing_list = ws + 4 + batch, *const acc_list = ws + 4 + 2 * batch, *const ns_list = acc_list;
         hipError_t e;
+        if constexpr (F64) {
+            if (front) {
+                const unsigned b = (unsigned)batch;
+                hipLaunchKernelGGL((matinv_gj_tile_f64<4, true, true, false, true>), dim3(tile_grid(batch, 12u)), dim3(64), 0, stream, A, X, info,
+                                   n, b, rej_count, rej_list, ns_count, ns_list);
+                hipLaunchKernelGGL((matinv_gj_tile_f64<4, true, true>), dim3(tile_grid(batch, 8u, 1u)), dim3(64), 0, stream, A, X, info, n, b,
+                                   rej_count, rej_list, ns_count, ns_list);
+                e = hipGetLastError();
+                if (e == hipSuccess)
+                    e = launch_gj_tilep_worklist<T>(n, A, X, batch, rej_count, rej_list, sing_count, sing_list, info, stream,
+                                                    tile_policy_record(F64, s.nt, batch), false, ns_count, tile_policy_record_sym_front(s.nt));
+                return e;
+            }
+        }
         if (rowlane2) {
             e = enqueue_gj_rowlane2<T>(n, A, X, batch, info, stream, rej_count, rej_list);
         } else {

@@ -137,6 +137,69 @@ bool tile_policy_use_screen(bool f64, int nt)
     return batch > 0 && 4ull * rejected >= batch;
 }
 
+// ---- 64 x 64 fp64, unscreened: symmetric-only kernel in front, or the two-arm kernel alone? (launch_gj_tile_natural) ------------
+// The FRONT route pays one more small launch and, for every matrix that is not symmetric, a second set of loads; the DIRECT route
+// runs a symmetric matrix at two waves per SIMD instead of three. The choice follows launch history like the screening pass does and
+// never changes a result: FRONT unless the last front launch of this device and tile count that has COMPLETED found at least a
+// quarter of its batch not symmetric -- that count comes back like the reject hint, one 8-byte store of the work-list kernel that
+// ends the chain into pinned host memory, never waited for -- and in that state every 32nd launch probes the front route again.
+namespace {
+struct FrontSlot {
+    std::atomic<unsigned long long> pair;  // (batch << 32) | not symmetric, of the last completed front launch: device store
+    std::atomic<unsigned> launches_in_direct_mode;
+};
+FrontSlot *front_slots()
+{
+    static FrontSlot *slots = []() -> FrontSlot * {
+        void *p = nullptr;
+        if (hipHostMalloc(&p, sizeof(FrontSlot) * kMaxDevices * kSlotsPerDevice, hipHostMallocPortable) != hipSuccess) return nullptr;
+        memset(p, 0, sizeof(FrontSlot) * kMaxDevices * kSlotsPerDevice);
+        return static_cast<FrontSlot *>(p);
+    }();
+    return slots;
+}
+std::atomic<unsigned long long> g_front_launches{0}, g_direct_launches{0};
+std::atomic<int> g_last_front_slot{0};
+}  // namespace
+
+bool tile_policy_use_sym_front(int nt)
+{
+    FrontSlot *h = front_slots();
+    bool front = h != nullptr;  // without the slots nobody would ever learn that a batch is not symmetric
+    if (h) {
+        const int idx = slot_index(true, nt);
+        g_last_front_slot.store(idx, std::memory_order_relaxed);
+        const unsigned long long pr = h[idx].pair.load(std::memory_order_relaxed);
+        const unsigned long long batch = pr >> 32, notsym = pr & 0xffffffffull;
+        if (batch > 0 && 4ull * notsym >= batch)
+            front = ((h[idx].launches_in_direct_mode.fetch_add(1, std::memory_order_relaxed) + 1) % 32u) == 0;  // every 32nd probes
+        else
+            h[idx].launches_in_direct_mode.store(0, std::memory_order_relaxed);
+    }
+    (front ? g_front_launches : g_direct_launches).fetch_add(1, std::memory_order_relaxed);
+    return front;
+}
+
+// before a front launch: where the work-list kernel behind it stores (batch << 32) | not symmetric
+hint_t *tile_policy_record_sym_front(int nt)
+{
+    FrontSlot *h = front_slots();
+    static_assert(sizeof(std::atomic<unsigned long long>) == sizeof(hint_t), "the device stores into the atomic's storage");
+    return h ? reinterpret_cast<hint_t *>(&h[slot_index(true, nt)].pair) : nullptr;
+}
+
+SymFrontStats sym_front_stats()
+{
+    FrontSlot *h = front_slots();
+    SymFrontStats t{g_front_launches.load(), g_direct_launches.load(), 0, 0};
+    if (h) {
+        const unsigned long long pr = h[g_last_front_slot.load()].pair.load(std::memory_order_relaxed);
+        t.last_not_symmetric = pr & 0xffffffffull;
+        t.last_batch = pr >> 32;
+    }
+    return t;
+}
+
 TileStats tile_stats()
 {
     HintSlot *h = hint_slots();

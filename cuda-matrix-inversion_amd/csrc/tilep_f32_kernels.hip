@@ -5,6 +5,6 @@ namespace matinv {
 
 template hipError_t launch_gj_tilep<float>(int, BatchRef<const float>, BatchRef<float>, size_t, int *, hipStream_t);
 template hipError_t launch_gj_tilep_worklist<float>(int, BatchRef<const float>, BatchRef<float>, size_t, const int *, const int *, int *,
-                                                    int *, int *, hipStream_t, hint_t *, bool);
+                                                    int *, int *, hipStream_t, hint_t *, bool, const int *, hint_t *);
 
 }  // namespace matinv

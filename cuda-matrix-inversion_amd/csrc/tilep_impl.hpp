@@ -166,7 +166,7 @@ struct IntC {
 template <class T, int NT, bool FULL>
 __device__ __forceinline__ void gj_tilep_body(BatchRef<const T> Ain, BatchRef<T> Xout, int *info, int n_rt, unsigned batch,
                                               T *lds, unsigned char *tab, const int *in_count, const int *in_list, hint_t *hint_out,
-                                              int *bad_count, int *bad_list)
+                                              int *bad_count, int *bad_list, const int *aux_count, hint_t *aux_out)
 {
     typedef TileGeo<T> G;
     typedef typename G::vec4 vec4;
@@ -184,6 +184,9 @@ __device__ __forceinline__ void gj_tilep_body(BatchRef<const T> Ain, BatchRef<T>
     // work-list form: the length of the list is what the launcher's natural-order / pivot guess feeds on; it goes back to
     // the host through a store into pinned memory (no copy command in the stream, nobody waits for it)
     if (hint_out && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(hint_out, ((hint_t)batch << 32) | todo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // a second count of the chain in front of this kernel (the not-symmetric list of the 64 x 64 fp64 front route), back the same way
+    if (aux_out && blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_store(aux_out, ((hint_t)batch << 32) | (unsigned)*aux_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     for (unsigned item = blockIdx.x; item < todo; item += gridDim.x) {
         const unsigned mat = in_list ? (unsigned)in_list[item] : item;
         const T *A = Ain.at_uniform(mat);
@@ -431,28 +434,29 @@ __device__ __forceinline__ void gj_tilep_body(BatchRef<const T> Ain, BatchRef<T>
 template <int NT, bool FULL>
 __global__ __launch_bounds__(64, 3) void matinv_gj_tilep_f64(BatchRef<const double> Ain, BatchRef<double> Xout, int *info, int n_rt,
                                                             unsigned batch, const int *in_count, const int *in_list, hint_t *hint_out,
-                                                            int *bad_count, int *bad_list)
+                                                            int *bad_count, int *bad_list, const int *aux_count, hint_t *aux_out)
 {
     __shared__ __attribute__((aligned(16))) double lds[256 + 4 * 16 * NT];
     __shared__ unsigned char tab[128];
-    gj_tilep_body<double, NT, FULL>(Ain, Xout, info, n_rt, batch, lds, tab, in_count, in_list, hint_out, bad_count, bad_list);
+    gj_tilep_body<double, NT, FULL>(Ain, Xout, info, n_rt, batch, lds, tab, in_count, in_list, hint_out, bad_count, bad_list, aux_count, aux_out);
 }
 
 template <int NT, bool FULL>
 __global__ __launch_bounds__(64, 3) void matinv_gj_tilep_f32(BatchRef<const float> Ain, BatchRef<float> Xout, int *info, int n_rt,
                                                             unsigned batch, const int *in_count, const int *in_list, hint_t *hint_out,
-                                                            int *bad_count, int *bad_list)
+                                                            int *bad_count, int *bad_list, const int *aux_count, hint_t *aux_out)
 {
     __shared__ __attribute__((aligned(16))) float lds[256 + 4 * 16 * NT];
     __shared__ unsigned char tab[128];
-    gj_tilep_body<float, NT, FULL>(Ain, Xout, info, n_rt, batch, lds, tab, in_count, in_list, hint_out, bad_count, bad_list);
+    gj_tilep_body<float, NT, FULL>(Ain, Xout, info, n_rt, batch, lds, tab, in_count, in_list, hint_out, bad_count, bad_list, aux_count, aux_out);
 }
 
 // in_count / in_list != nullptr: work-list form (one round of resident workgroups strides over the list; usually empty).
 // Singular matrices are appended to (bad_count, bad_list) for the ROW kernel.
 template <class T>
 static hipError_t enqueue_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *info, hipStream_t stream,
-                                const int *in_count, const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list, bool expect_many = false)
+                                const int *in_count, const int *in_list, hint_t *hint_out, int *bad_count, int *bad_list, bool expect_many = false,
+                                const int *aux_count = nullptr, hint_t *aux_out = nullptr)
 {
     // work-list form: the list is usually empty -- one round of resident workgroups that stride over it. Behind the screening pass
     // (expect_many) most of the batch is on it: one workgroup per matrix as in the direct form (a workgroup beyond the list's
@@ -461,10 +465,10 @@ static hipError_t enqueue_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_
     with_tile<1, 4>(tile_shape(n), [&](auto NT, auto FULL) {
         if constexpr (sizeof(T) == 8)
             hipLaunchKernelGGL((matinv_gj_tilep_f64<NT, FULL>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out,
-                               bad_count, bad_list);
+                               bad_count, bad_list, aux_count, aux_out);
         else
             hipLaunchKernelGGL((matinv_gj_tilep_f32<NT, FULL>), dim3(grid), dim3(64), 0, stream, A, X, info, n, b, in_count, in_list, hint_out,
-                               bad_count, bad_list);
+                               bad_count, bad_list, aux_count, aux_out);
     });
     return hipGetLastError();
 }
@@ -485,9 +489,10 @@ hipError_t launch_gj_tilep(int n, BatchRef<const T> A, BatchRef<T> X, size_t bat
 // to the ROW kernel through (bad_count, bad_list), which the caller has zeroed
 template <class T>
 hipError_t launch_gj_tilep_worklist(int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, const int *in_count, const int *in_list,
-                                    int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many)
+                                    int *bad_count, int *bad_list, int *info, hipStream_t stream, hint_t *hint_out, bool expect_many,
+                                    const int *aux_count, hint_t *aux_out)
 {
-    hipError_t e = enqueue_tilep<T>(n, A, X, batch, info, stream, in_count, in_list, hint_out, bad_count, bad_list, expect_many);
+    hipError_t e = enqueue_tilep<T>(n, A, X, batch, info, stream, in_count, in_list, hint_out, bad_count, bad_list, expect_many, aux_count, aux_out);
     if (e == hipSuccess) e = launch_gj_row_worklist<T>(n, A, X, bad_count, bad_list, info, stream);
     if (e == hipSuccess) e = debug_note_rejects(in_count, stream);
     return e;

@@ -7,7 +7,7 @@ bool tilep_supports(int n) { return n >= 1 && n <= 128; }
 
 template hipError_t launch_gj_tilep<double>(int, BatchRef<const double>, BatchRef<double>, size_t, int *, hipStream_t);
 template hipError_t launch_gj_tilep_worklist<double>(int, BatchRef<const double>, BatchRef<double>, size_t, const int *, const int *, int *,
-                                                     int *, int *, hipStream_t, hint_t *, bool);
+                                                     int *, int *, hipStream_t, hint_t *, bool, const int *, hint_t *);
 
 const char *name_gj_tilep(bool f64, int n)
 {

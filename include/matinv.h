@@ -299,6 +299,11 @@ int matinv_device_synchronize(void);
  * launch whose count has come back (call matinv_device_synchronize first for an exact figure). Any pointer may be NULL. */
 int matinv_tile_stats(unsigned long long *natural_launches, unsigned long long *pivot_launches, unsigned long long *last_rejected,
                       unsigned long long *last_batch);
+/* Unscreened 64 x 64 fp64 Gauss-Jordan launches since load: those that ran the symmetric-only kernel in front of the two-arm kernel /
+ * the two-arm kernel alone, and how many matrices the last front launch whose count has come back found not symmetric, of how many
+ * (call matinv_device_synchronize first for an exact figure). The route never changes a result. Any pointer may be NULL. */
+int matinv_sym_front_stats(unsigned long long *front_launches, unsigned long long *direct_launches, unsigned long long *last_not_symmetric,
+                           unsigned long long *last_batch);
 
 /* Size-binned multi-queue for mixed-size pipeline items (the reference sketches it, README.md:41-44: "use multiple queues
  * for different sizes: 32, 128, 512, 1024"; BASELINE configs[4]). Items of any n <= the largest bin are submitted as
