@@ -501,6 +501,87 @@ def logml_grad_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_logml_grad_kernel_name(code, n).decode()
 
 
+_PREDICT_OUTPUTS = ("mean", "var")
+
+
+def predict_batched(n, Bs, Cs, Ds, As, Es, mean=None, var=None, batchSize=None, info=None, want=_PREDICT_OUTPUTS):
+    """GP prediction at Q query points per covariance matrix on device tensors (matinv_predict_batched; asynchronous on torch's current
+    stream). With M_k = B_k + diag c_k, K = M^-1 and alpha = K d:  mean[k, j] = a_kj^T alpha_k,  var[k, j] = e_kj - a_kj^T K_k a_kj  for the
+    Q cross-covariance vectors of matrix k (As: batchSize*Q*n elements, vector (k, j) at (k*Q + j)*n) and their prior variances (Es:
+    batchSize*Q elements, or None for e = 0). Q is As.numel() // (batchSize*n).
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one. Cs may be None (M = B),
+    Ds may be None when mean is not asked for. Only B's lower triangle is read, no input is modified and var is not clamped.
+    Returns (mean, var), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Ds, As, Es, mean, var, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    unknown = set(want) - set(_PREDICT_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_PREDICT_OUTPUTS}")
+    if mean is None and var is None and not want:
+        raise ValueError("no output requested")
+    if As is None:
+        raise ValueError("prediction needs the cross-covariance vectors As")
+    nquery = As.numel() // (batchSize * n) if batchSize else 0
+    if batchSize and (nquery < 1 or As.numel() < batchSize * nquery * n):
+        raise ValueError("As needs batchSize*Q*n elements, Q >= 1")
+    if mean is None and "mean" in want:
+        mean = torch.empty(batchSize * nquery, dtype=Bs.dtype, device=Bs.device)
+    if var is None and "var" in want:
+        var = torch.empty(batchSize * nquery, dtype=Bs.dtype, device=Bs.device)
+    if mean is not None and Ds is None:
+        raise ValueError("mean needs the observations Ds")
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, As, Es, mean, var)):
+        raise TypeError("Bs, Cs, Ds, As, Es, mean and var must have one dtype")
+    if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds)) or \
+            any(t is not None and t.numel() < batchSize * nquery for t in (Es, mean, var)):
+        raise ValueError("Cs and Ds need batchSize*n elements, Es, mean and var batchSize*Q")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_predict_batched(
+            _torch_dtype_code(Bs), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es), p(mean), p(var), batchSize,
+            p(info), _stream_ptr(Bs)))
+    return mean, var
+
+
+def predict_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, want=_PREDICT_OUTPUTS):
+    """matinv_predict_batched_host on numpy batches (packed; Cs and Es may be None, Ds may be None without "mean" in want): returns
+    (mean, var, info), None for the outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    As = np.ascontiguousarray(As)
+    Cs, Ds, Es = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Ds, Es))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, As, Es)):
+        raise TypeError("Bs, Cs, Ds, As and Es must have one dtype")
+    unknown = set(want) - set(_PREDICT_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_PREDICT_OUTPUTS}")
+    batch = Bs.size // (n * n)
+    nquery = As.size // (batch * n) if batch else 0
+    if batch and nquery < 1:
+        raise ValueError("As needs batch*Q*n elements, Q >= 1")
+    if "mean" in want and Ds is None:
+        raise ValueError("mean needs the observations Ds")
+    if any(t is not None and t.size < batch * n for t in (Cs, Ds)) or (Es is not None and Es.size < batch * nquery):
+        raise ValueError("Cs and Ds smaller than batch*n, or Es smaller than batch*Q")
+    mean = np.empty(batch * nquery, dtype=Bs.dtype) if "mean" in want else None
+    var = np.empty(batch * nquery, dtype=Bs.dtype) if "var" in want else None
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_predict_batched_host(
+        _np_dtype_code(Bs.dtype), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es), p(mean), p(var), batch,
+        p(info)))
+    return mean, var, info
+
+
+def predict_kernel_name(dtype, n: int) -> str:
+    """matinv_predict_kernel_name: the kernel a prediction request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_predict_kernel_name(code, n).decode()
+
+
 def logdet_kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> str:
     """matinv_logdet_kernel_name: the kernel a logdet request launches ("" when the request would be refused)."""
     code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)

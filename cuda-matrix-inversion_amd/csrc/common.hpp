@@ -373,6 +373,20 @@ hipError_t launch_logml_grad_global(int n, int nparam, const T *Bs, const T *Cs,
                                     size_t batch, int *info, hipStream_t stream);
 const char *name_logml_grad_global(bool f64);
 
+// Batched GP prediction at nquery query points per matrix (matinv_predict_batched): As: batch * nquery vectors of n elements, Es (optional):
+// batch * nquery prior variances; mean, var: batch * nquery, each optional. Ds is read with mean only.
+// (a) the prediction form of the one-wavefront SPD sweep, n <= 96 (predict_tile_kernels.hip, predict_tile_f32_kernels.hip)
+bool predict_tile_supports(int n);
+template <class T>
+hipError_t launch_predict_tile(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *var,
+                               size_t batch, int *info, hipStream_t stream);
+const char *name_predict_tile(bool f64, int n);
+// (b) the prediction form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_predict_global(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *var,
+                                 size_t batch, int *info, hipStream_t stream);
+const char *name_predict_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

@@ -489,4 +489,139 @@ const char *name_logml_grad_global(bool f64)
     return f64 ? "matinv_chol_global<double, true, true>" : "matinv_chol_global<float, true, true>";
 }
 
+// ---- GP prediction at many query points, 96 < n <= 1024 (matinv_predict_batched behind predict_tile_impl.hpp) --------------------------
+// The prediction form of matinv_chol_global: one more template argument again ("Prediction at many query points").
+// M = B + diag c is factored in a working copy in library scratch and the factor inverted in place, as above; then
+//     alpha = L^-T (L^-1 d)                            (the two triangular products of the LOO form; only when mean is asked for)
+//     per query j:  v = L^-1 a_j                       (a triangular product, a_j in an LDS vector, one thread per row)
+//                   var_j = e_j - sum_k v_k^2,   mean_j = sum_k a_jk alpha_k      (both on the fixed LDS tree)
+// one query after the other in an order that knows nothing of Q. Not SPD: info = the failing column + 1 and every output NaN. Correct
+// first; speed is not a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x.
+template <class T, bool LOO, bool GRAD, bool PREDICT>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Ds, const T *As, int nquery, const T *Es,
+                                                                 T *mean, T *var, int *info, int n, T *workspace, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT, "the four-argument form is the prediction kernel");
+    __shared__ T col[1024], va[1024], vy[1024], vq[1024];
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    T *W = workspace + (size_t)blockIdx.x * n * n;
+    const int t = threadIdx.x;
+    const size_t nn = (size_t)n * n;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    if (mean)
+        for (int i = t; i < n; i += GL_THREADS) va[i] = Ds[k_mat * n + i];
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        for (int j = t; j < nquery; j += GL_THREADS) {
+            if (mean) mean[k_mat * nquery + j] = nan_of<T>();
+            if (var) var[k_mat * nquery + j] = nan_of<T>();
+        }
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+        const T ajj = (T)1 / W[(size_t)j * n + j];
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+        __syncthreads();
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+            W[(size_t)j * n + i] = -s * ajj;
+        }
+        if (t == 0) W[(size_t)j * n + j] = ajj;
+        __syncthreads();
+    }
+    if (mean) {  // block-uniform
+        // y = L^-1 d: (L^-1)_kj sits at W[j*n + k]
+        for (int k = t; k < n; k += GL_THREADS) {
+            T s = 0;
+            for (int j = 0; j <= k; ++j) s += W[(size_t)j * n + k] * va[j];
+            vy[k] = s;
+        }
+        __syncthreads();
+        // alpha_i = column i of L^-1 against y; it takes the place of d
+        for (int i = t; i < n; i += GL_THREADS) {
+            T a = 0;
+            for (int k = i; k < n; ++k) a += W[(size_t)i * n + k] * vy[k];
+            va[i] = a;
+        }
+        __syncthreads();
+    }
+    for (int j = 0; j < nquery; ++j) {
+        const size_t out = k_mat * nquery + j;
+        const T *a = As + out * n;
+        for (int i = t; i < n; i += GL_THREADS) vq[i] = a[i];
+        __syncthreads();
+        T sq = 0, sm = 0;
+        for (int k = t; k < n; k += GL_THREADS) {
+            if (var) {  // v_k = row k of L^-1 against a
+                T s = 0;
+                for (int i = 0; i <= k; ++i) s += W[(size_t)i * n + k] * vq[i];
+                sq += s * s;
+            }
+            if (mean) sm += vq[k] * va[k];
+        }
+        // block sums on a fixed tree
+        col[t] = sq;
+        vy[t] = sm;
+        __syncthreads();
+        for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+            if (t < off) {
+                col[t] += col[t + off];
+                vy[t] += vy[t + off];
+            }
+            __syncthreads();
+        }
+        if (t == 0) {
+            if (var) var[out] = (Es ? Es[out] : (T)0) - col[0];
+            if (mean) mean[out] = vy[0];
+        }
+        __syncthreads();  // the next query overwrites vq, col and vy
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_predict_global(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *var,
+                                 size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_loo_global)
+    const size_t mat = (size_t)n * n;
+    size_t chunk = blocked_workspace_cap() / (mat * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * mat * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Bs, Cs, Ds, As, nquery,
+                           Es, mean, var, info, n, ws, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_predict_global<double>(int, int, const double *, const double *, const double *, const double *, const double *,
+                                                  double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_predict_global<float>(int, int, const float *, const float *, const float *, const float *, const float *, float *,
+                                                 float *, size_t, int *, hipStream_t);
+
+const char *name_predict_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true>" : "matinv_chol_global<float, true, true, true>";
+}
+
 }  // namespace matinv

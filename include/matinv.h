@@ -243,6 +243,30 @@ const char *matinv_logml_grad_kernel_name(int dtype, int n);
 int matinv_logml_grad_batched_host(int dtype, int n, int nparam, const void *hBs, const void *hCs, const void *hDs, const void *hDMs,
                                    void *hGrad, void *hGradC, void *hAlpha, size_t batch, int *info);
 
+/* Gaussian-process prediction at nquery query points per covariance matrix, device-resident. With M_k = B_k + diag(c_k), K = M^-1,
+ * alpha = K d, a_kj the cross-covariance vector of query j of matrix k (n elements) and e_kj its prior variance:
+ *   mean[k*nquery + j] = a_kj^T alpha_k                 the predictive mean
+ *   var[k*nquery + j]  = e_kj - a_kj^T K_k a_kj         the predictive variance of the latent function
+ * For nquery = 1 this is what matinv_mean_batched / matinv_variance_batched compute, without a second factorisation for the second
+ * output and without one per query beyond. B, c, d as in matinv_loo_batched (SPD, column-major, only the lower triangle read; dCs may be
+ * NULL). dAs: batch*nquery*n elements, vector (k, j) at offset (k*nquery + j)*n, i.e. the n x nquery cross-covariance matrix of item k
+ * in column-major order. dEs: batch*nquery elements, or NULL (e = 0: var is then minus the variance reduction). dMean, dVar:
+ * batch*nquery elements; each may be NULL (both NULL: MATINV_ERR_ARG), and which of them is requested does not change a bit of the
+ * other. dDs is read only with dMean, dEs only with dVar. nquery >= 1. var is not clamped: a tiny negative value from cancellation
+ * is the caller's to see. No input is modified (outputs must not overlap inputs); neither M nor its inverse is written to caller
+ * memory; the result for (k, j) depends on matrix k and query j alone, bit for bit -- not on batch, nquery or the position of j among
+ * the queries. dInfo (optional): 0, or the 1-based column of the first non-positive (or NaN) pivot -- every output of that matrix is
+ * then NaN. n <= 96: the prediction form of the one-wavefront SPD tile sweep, the queries in groups of 16 on the MFMA unit
+ * (n^2/2 + 2n + nquery (n + 1) elements read, 2 nquery written). Beyond, to n = 1024: the prediction form of the global-memory
+ * Cholesky kernel on a working copy in library scratch. Asynchronous, no host synchronisation. */
+int matinv_predict_batched(int dtype, int n, int nquery, const void *dBs, const void *dCs, const void *dDs, const void *dAs, const void *dEs,
+                           void *dMean, void *dVar, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a prediction request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_predict_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, hEs, `info` and each output optional; hDs is read only with hMean). Synchronous. */
+int matinv_predict_batched_host(int dtype, int n, int nquery, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
+                                const void *hEs, void *hMean, void *hVar, size_t batch, int *info);
+
 /* Host-pointer convenience used by the reference-named *_gpu wrappers: allocate, H2D, invert, D2H, free.
  * `info` is an optional host int[batch]. Synchronous. */
 int matinv_inverse_batched_host(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info);
