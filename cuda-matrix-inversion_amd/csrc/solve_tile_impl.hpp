@@ -5,14 +5,18 @@
 // sits in the NT x NT accumulator tiles exactly as there, and Z = B^T rides below it (row r of Z = column r of B, contiguous
 // in memory, loaded like a row of W; rows nrhs .. 15 are zero). Every block step is the same blocked in-place step
 //     Aop[i,:] = -W[i,K] D^-1,   W[i,J] += Aop[i,:] W[K,J],   W[:,K] <- Aop        (one 16x16x4 MFMA per tile)
-// applied to the border and to the tile rows that still hold unpivoted rows only: a row that has been a pivot row is never
-// read again, so tile rows above the pivot block's are dropped from the update. After the last block step the border holds
-// -X^T (S = [A^T; B^T] swept on its first n rows: the border ends as -B^T A^-T), stored negated like a row of W, which gives
-// column-major X. 4 NT (NT (NT + 1) / 2 + NT) MFMAs per matrix: 224 at n = 64 against 256 for the inverse, and n^2 + 2 n nrhs
-// elements of traffic against 2 n^2.
+// applied to the border and to the tile rows that still hold unpivoted rows: the solution needs nothing of a row that has been
+// a pivot row, so the Cholesky form drops the tile rows above the pivot block's from the update. After the last block step the
+// border holds -X^T (S = [A^T; B^T] swept on its first n rows: the border ends as -B^T A^-T), stored negated like a row of W,
+// which gives column-major X. The Gauss-Jordan form carries the pivoted tile rows along all the same, through the tile columns
+// still to be pivoted, because the verdict needs their multipliers (below). MFMAs per matrix: Cholesky 4 NT (NT (NT + 1) / 2 + NT),
+// Gauss-Jordan 2 NT (NT^2 - 1) / 3 more -- 224 and 264 at n = 64 against 256 for the inverse -- and n^2 + 2 n nrhs elements of
+// traffic against 2 n^2.
 //
 // Acceptance (rows of W only; B's entries never cause a rejection):
-//   Gauss-Jordan: the natural-order kernel's threshold test (every multiplier |m| <= TILE_TAU, NaN fails). A matrix that fails
+//   Gauss-Jordan: the natural-order kernel's threshold test (every multiplier |m| <= TILE_TAU, NaN fails), on EVERY row of W
+//                 outside the pivot block, the rows already pivoted included: a matrix gets the verdict that inverse_batched
+//                 gives it, whichever entry point it comes through (tests/test_gpu_accept.py counts both). A matrix that fails
 //                 goes to a device work list and is solved again, in the same stream, by the partially pivoted row solve
 //                 (solve_row_kernels.hip) -- which also reports a singular matrix's info exactly like the inverse's pivoting kernels.
 //   Cholesky:     A is read from its lower triangle only (W is built symmetric) and every pivot must be positive. The kernel
@@ -24,17 +28,17 @@ namespace matinv {
 
 constexpr int SOLVE_MAX_NRHS = 16;
 
-// 1. the 4 pivot columns of block kb of the live tile rows and of the border -> LDS, [row][4]; the border is panel row 16 NT + z
+// 1. the 4 pivot columns of block kb of the tile rows t0 .. NT - 1 and of the border -> LDS, [row][4]; the border is panel row 16 NT + z
 template <int NT, class T>
 __device__ __forceinline__ void solve_panel_to_lds(T *panel, const typename TileGeo<T>::vec4 (&acc)[NT][NT],
-                                                   const typename TileGeo<T>::vec4 (&zacc)[NT], int kb, int q, int c)
+                                                   const typename TileGeo<T>::vec4 (&zacc)[NT], int kb, int t0, int q, int c)
 {
     typedef TileGeo<T> G;
     const int tK = kb >> 2, rK = kb & 3;
     if (G::blk(c) == rK) {
 #pragma unroll
         for (int ti = 0; ti < NT; ++ti) {
-            if (ti < tK) continue;  // pivoted rows only: never read again
+            if (ti < t0) continue;
 #pragma unroll
             for (int r = 0; r < 4; ++r) panel[(16 * ti + G::trow(r, q)) * 4 + G::piv(c)] = acc[ti][tK][r];
         }
@@ -43,11 +47,11 @@ __device__ __forceinline__ void solve_panel_to_lds(T *panel, const typename Tile
     }
 }
 
-// 5.+6. B operand (pivot rows as they stand, I_4 on the pivot columns) and C operand (zero on the pivot columns) of the live tile
-// rows and the border -- prep_operands of tile_impl.hpp restricted to those rows; asm for the reasons given there.
+// 5.+6. B operand (pivot rows as they stand, I_4 on the pivot columns) and C operand (zero on the pivot columns) of the tile
+// rows t0 .. NT - 1 and the border -- prep_operands of tile_impl.hpp restricted to those rows; asm for the reasons given there.
 template <int NT, class T>
 __device__ __forceinline__ void solve_prep_operands(typename TileGeo<T>::vec4 (&acc)[NT][NT], typename TileGeo<T>::vec4 (&zacc)[NT],
-                                                    T (&bop)[NT], int kb, int q, int c)
+                                                    T (&bop)[NT], int kb, int t0, int q, int c)
 {
     typedef TileGeo<T> G;
     typedef typename G::vec4 vec4;
@@ -90,7 +94,7 @@ __device__ __forceinline__ void solve_prep_operands(typename TileGeo<T>::vec4 (&
     };
 #pragma unroll
     for (int ti = 0; ti < NT; ++ti) {
-        if (ti < tK) continue;
+        if (ti < t0) continue;
         zero_cols(acc[ti][tK]);
     }
     zero_cols(zacc[tK]);
@@ -180,7 +184,9 @@ __device__ __forceinline__ void solve_tile_body(BatchRef<const T> Ain, BatchRef<
         for (int kb = 0; kb < NKB; ++kb) {
             if (!FULL && kb > 4 * (NT - 1) && kb - 4 * (NT - 1) >= G::real_blocks(n - 16 * (NT - 1))) continue;  // all padding
             const int tK = kb >> 2;
-            solve_panel_to_lds<NT, T>(panel, acc, zacc, kb, q, c);
+            // Gauss-Jordan: the tile rows above the pivot block's come along for their multipliers alone (see the head of the file)
+            const int t0 = SPD ? tK : 0;
+            solve_panel_to_lds<NT, T>(panel, acc, zacc, kb, t0, q, c);
             wave_lds_sync();
             {
                 PanelSolve<NT, SPD, T> ps;
@@ -189,18 +195,21 @@ __device__ __forceinline__ void solve_tile_body(BatchRef<const T> Ain, BatchRef<
                 for (int s = 0; s < 6; ++s) ps.stage(s, panel, kb, q, c, aop, bad);
 #pragma unroll
                 for (int ti = 0; ti < NT; ++ti)
-                    if (ti >= tK) ps.stage(6 + ti, panel, kb, q, c, aop, bad);
+                    if (ti >= t0) ps.stage(6 + ti, panel, kb, q, c, aop, bad);
                 // border: Zop[z,:] = -Z[z,K] D^-1 (lane c = border row c, column q), exempt from the test
                 const T *w = &panel[(16 * NT + c) * 4];
                 zop = -fma_t(w[3], ps.x3, fma_t(w[2], ps.x2, fma_t(w[1], ps.x1, w[0] * ps.x0)));
             }
             wave_lds_sync();  // the panel is rewritten by the next block step
-            solve_prep_operands<NT, T>(acc, zacc, bop, kb, q, c);
+            solve_prep_operands<NT, T>(acc, zacc, bop, kb, t0, q, c);
 #pragma unroll
             for (int ti = 0; ti < NT; ++ti) {
-                if (ti < tK) continue;
+                if (ti < t0) continue;
 #pragma unroll
-                for (int tj = 0; tj < NT; ++tj) acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
+                for (int tj = 0; tj < NT; ++tj) {
+                    if (ti < tK && tj < tK) continue;  // a pivoted row's pivoted columns: no later multiplier reads them
+                    acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
+                }
             }
 #pragma unroll
             for (int tj = 0; tj < NT; ++tj) zacc[tj] = G::mfma(zop, bop[tj], zacc[tj]);

@@ -58,7 +58,7 @@ U = {"f64": 2.0 ** -53, "f32": 2.0 ** -24}
 # grid = tile_grid(batch, per_cu) = 256 * per_cu workgroups (csrc/common.hpp:169). tests/test_grid_stride_cpu.py fails when a launch
 # site asks for more per CU than assumed here.
 ONE_WAVE_PER_CU = 16   # largest per-CU figure of a 64-thread launch: csrc/tile_impl.hpp:1070 (fp32), :1071 (screening pass),
-#                        csrc/tile_f32_kernels.hip:17, csrc/solve_tile_impl.hpp:276; 12 at csrc/tile_impl.hpp:1055, csrc/tile_kernels.hip:250,
+#                        csrc/tile_f32_kernels.hip:17, csrc/solve_tile_impl.hpp:285; 12 at csrc/tile_impl.hpp:1055, csrc/tile_kernels.hip:250,
 #                        csrc/tilep_impl.hpp:464; 8 at csrc/tile_impl.hpp:1134, csrc/gp_tile_impl.hpp:185, csrc/logdet_tile_impl.hpp:201
 MULTI_WAVE_PER_CU = 4  # workgroups of several wavefronts: csrc/spd_tile2_kernels.hip:20, csrc/tilep4_impl.hpp:404; 3 / 1 at
 #                        csrc/tile4_impl.hpp:314, 1 at csrc/tileq_impl.hpp:509
