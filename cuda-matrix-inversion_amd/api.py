@@ -582,6 +582,88 @@ def predict_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_predict_kernel_name(code, n).decode()
 
 
+_PREDICT_COV_OUTPUTS = ("mean", "cov")
+
+
+def predict_cov_batched(n, Bs, Cs, Ds, As, Es, mean=None, cov=None, batchSize=None, info=None, want=_PREDICT_COV_OUTPUTS):
+    """Joint predictive covariance between the Q query points of each covariance matrix on device tensors (matinv_predict_cov_batched;
+    asynchronous on torch's current stream). With M_k = B_k + diag c_k, K = M^-1 and alpha = K d:  mean[k, i] = a_ki^T alpha_k,
+    cov[k][j*Q + i] = E_k[i][j] - a_ki^T K_k a_kj  for the Q cross-covariance vectors of matrix k (As as in predict_batched) and the Q x Q
+    prior covariance between them (Es: batchSize*Q*Q elements, column-major per matrix, only the lower triangle read, or None for E = 0).
+    Q is As.numel() // (batchSize*n). cov (batchSize*Q*Q elements) has both triangles written and is exactly symmetric.
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one. Cs may be None (M = B),
+    Ds may be None when mean is not asked for. Only B's lower triangle is read, no input is modified and cov is not clamped.
+    Returns (mean, cov), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Ds, As, Es, mean, cov, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    unknown = set(want) - set(_PREDICT_COV_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_PREDICT_COV_OUTPUTS}")
+    if mean is None and cov is None and not want:
+        raise ValueError("no output requested")
+    if As is None:
+        raise ValueError("prediction needs the cross-covariance vectors As")
+    nquery = As.numel() // (batchSize * n) if batchSize else 0
+    if batchSize and (nquery < 1 or As.numel() < batchSize * nquery * n):
+        raise ValueError("As needs batchSize*Q*n elements, Q >= 1")
+    if mean is None and "mean" in want:
+        mean = torch.empty(batchSize * nquery, dtype=Bs.dtype, device=Bs.device)
+    if cov is None and "cov" in want:
+        cov = torch.empty(batchSize * nquery * nquery, dtype=Bs.dtype, device=Bs.device)
+    if mean is not None and Ds is None:
+        raise ValueError("mean needs the observations Ds")
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, As, Es, mean, cov)):
+        raise TypeError("Bs, Cs, Ds, As, Es, mean and cov must have one dtype")
+    if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds)) or (mean is not None and mean.numel() < batchSize * nquery) or \
+            any(t is not None and t.numel() < batchSize * nquery * nquery for t in (Es, cov)):
+        raise ValueError("Cs and Ds need batchSize*n elements, mean batchSize*Q, Es and cov batchSize*Q*Q")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_predict_cov_batched(
+            _torch_dtype_code(Bs), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es) if cov is not None else None,
+            p(mean), p(cov), batchSize, p(info), _stream_ptr(Bs)))
+    return mean, cov
+
+
+def predict_cov_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, want=_PREDICT_COV_OUTPUTS):
+    """matinv_predict_cov_batched_host on numpy batches (packed; Cs and Es may be None, Ds may be None without "mean" in want): returns
+    (mean, cov, info), None for the outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    As = np.ascontiguousarray(As)
+    Cs, Ds, Es = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Ds, Es))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, As, Es)):
+        raise TypeError("Bs, Cs, Ds, As and Es must have one dtype")
+    unknown = set(want) - set(_PREDICT_COV_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_PREDICT_COV_OUTPUTS}")
+    batch = Bs.size // (n * n)
+    nquery = As.size // (batch * n) if batch else 0
+    if batch and nquery < 1:
+        raise ValueError("As needs batch*Q*n elements, Q >= 1")
+    if "mean" in want and Ds is None:
+        raise ValueError("mean needs the observations Ds")
+    if any(t is not None and t.size < batch * n for t in (Cs, Ds)) or (Es is not None and Es.size < batch * nquery * nquery):
+        raise ValueError("Cs and Ds smaller than batch*n, or Es smaller than batch*Q*Q")
+    mean = np.empty(batch * nquery, dtype=Bs.dtype) if "mean" in want else None
+    cov = np.empty(batch * nquery * nquery, dtype=Bs.dtype) if "cov" in want else None
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_predict_cov_batched_host(
+        _np_dtype_code(Bs.dtype), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es) if cov is not None else None,
+        p(mean), p(cov), batch, p(info)))
+    return mean, cov, info
+
+
+def predict_cov_kernel_name(dtype, n: int) -> str:
+    """matinv_predict_cov_kernel_name: the kernel a predictive-covariance request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_predict_cov_kernel_name(code, n).decode()
+
+
 def logdet_kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> str:
     """matinv_logdet_kernel_name: the kernel a logdet request launches ("" when the request would be refused)."""
     code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)

@@ -1078,6 +1078,73 @@ int predict_host(int n, int nquery, const void *hBs, const void *hCs, const void
     return MATINV_OK;
 }
 
+// ---- batched joint predictive covariance between the query points of a matrix (matinv_predict_cov_batched) ----------------------------
+int predict_cov_check_args(int dtype, int n, int nquery, const void *dBs, const void *dDs, const void *dAs, const void *dMean,
+                           const void *dCov, size_t batch)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 (got %d)", nquery);
+    if (!dBs || !dAs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dMean && !dCov) return fail(MATINV_ERR_ARG, "no output requested (mean and cov are both null)");
+    if (dMean && !dDs) return fail(MATINV_ERR_ARG, "mean requested without the observations (dDs is null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    if (nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
+    return MATINV_OK;
+}
+
+// n <= 96: the covariance form of the one-wavefront SPD sweep. Beyond, to n = 1024: the covariance form of the global-memory Cholesky kernel.
+template <class T>
+int predict_cov_dispatch(int n, int nquery, const void *dBs, const void *dCs, const void *dDs, const void *dAs, const void *dEs, void *dMean,
+                         void *dCov, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *d = static_cast<const T *>(dDs);
+    const T *a = static_cast<const T *>(dAs), *e_ = static_cast<const T *>(dEs);
+    T *mean = static_cast<T *>(dMean), *cov = static_cast<T *>(dCov);
+    const hipError_t e = predict_cov_tile_supports(n)
+                             ? launch_predict_cov_tile<T>(n, nquery, B, c, d, a, e_, mean, cov, batch, dInfo, stream)
+                             : launch_predict_cov_global<T>(n, nquery, B, c, d, a, e_, mean, cov, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "predict_cov launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int predict_cov_host(int n, int nquery, const void *hBs, const void *hCs, const void *hDs, const void *hAs, const void *hEs, void *hMean,
+                     void *hCov, size_t batch, int *info)
+{
+    const size_t vec = (size_t)n * batch, mat = vec * n, qs = batch * (size_t)nquery, qq = qs * (size_t)nquery;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dA = nullptr, *dE = nullptr, *dMean = nullptr, *dCov = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dA), qs * (size_t)n * sizeof(T));
+    if (e == hipSuccess && hEs && hCov) e = staging_alloc(reinterpret_cast<void **>(&dE), qq * sizeof(T));
+    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMean), qs * sizeof(T));
+    if (e == hipSuccess && hCov) e = staging_alloc(reinterpret_cast<void **>(&dCov), qq * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hMean) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, hAs, qs * (size_t)n * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dE) e = hipMemcpy(dE, hEs, qq * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = predict_cov_dispatch<T>(n, nquery, dB, dC, dD, dA, dE, dMean, dCov, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMean, qs * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hCov) e = hipMemcpy(hCov, dCov, qq * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dA), staging_free(dE), staging_free(dMean), staging_free(dCov);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "predict_cov host<->device");
+    return MATINV_OK;
+}
+
 template <class T>
 int lu_kernel(int n)
 {
@@ -1453,6 +1520,31 @@ int matinv_predict_batched_host(int dtype, int n, int nquery, const void *hBs, c
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return predict_host<double>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hVar, batch, info);
     return predict_host<float>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hVar, batch, info);
+}
+
+int matinv_predict_cov_batched(int dtype, int n, int nquery, const void *dBs, const void *dCs, const void *dDs, const void *dAs,
+                               const void *dEs, void *dMean, void *dCov, size_t batch, int *dInfo, void *stream)
+{
+    int rc = predict_cov_check_args(dtype, n, nquery, dBs, dDs, dAs, dMean, dCov, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return predict_cov_dispatch<double>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dCov, batch, dInfo, st);
+    return predict_cov_dispatch<float>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dCov, batch, dInfo, st);
+}
+
+const char *matinv_predict_cov_kernel_name(int dtype, int n)
+{
+    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return predict_cov_tile_supports(n) ? name_predict_cov_tile(dtype == MATINV_F64, n) : name_predict_cov_global(dtype == MATINV_F64);
+}
+
+int matinv_predict_cov_batched_host(int dtype, int n, int nquery, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
+                                    const void *hEs, void *hMean, void *hCov, size_t batch, int *info)
+{
+    int rc = predict_cov_check_args(dtype, n, nquery, hBs, hDs, hAs, hMean, hCov, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return predict_cov_host<double>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
+    return predict_cov_host<float>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
 }
 
 int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dDs,

@@ -387,6 +387,21 @@ hipError_t launch_predict_global(int n, int nquery, const T *Bs, const T *Cs, co
                                  size_t batch, int *info, hipStream_t stream);
 const char *name_predict_global(bool f64);
 
+// Batched joint predictive covariance between nquery query points per matrix (matinv_predict_cov_batched): As as above; Es (optional):
+// batch * nquery^2, column-major per matrix, lower triangle read; mean: batch * nquery, cov: batch * nquery^2 (both triangles written),
+// each optional. Ds is read with mean only, Es with cov only.
+// (a) the covariance form of the one-wavefront SPD sweep, n <= 96 (predict_cov_tile_kernels.hip, predict_cov_tile_f32_kernels.hip)
+bool predict_cov_tile_supports(int n);
+template <class T>
+hipError_t launch_predict_cov_tile(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *cov,
+                                   size_t batch, int *info, hipStream_t stream);
+const char *name_predict_cov_tile(bool f64, int n);
+// (b) the covariance form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_predict_cov_global(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *cov,
+                                     size_t batch, int *info, hipStream_t stream);
+const char *name_predict_cov_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

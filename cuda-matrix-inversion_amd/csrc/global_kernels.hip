@@ -624,4 +624,149 @@ const char *name_predict_global(bool f64)
     return f64 ? "matinv_chol_global<double, true, true, true>" : "matinv_chol_global<float, true, true, true>";
 }
 
+// ---- joint predictive covariance between the query points, 96 < n <= 1024 (matinv_predict_cov_batched behind predict_cov_tile_impl.hpp) ---
+// The covariance form of matinv_chol_global: one more template argument again ("Joint predictive covariance"). M = B + diag c
+// is factored in the matrix's slice of library scratch and the factor inverted in place, as above; the slice is n (n + Q) elements, the
+// last n Q of them V = L^-1 A (column-major, n x Q). Then
+//     alpha, mean_j                                   (the code of the prediction form, for the same bits)
+//     per query j:  V[:, j] = L^-1 a_j                (the triangular product of the prediction form, kept instead of squared and summed)
+//     per pair i >= j, one thread each:  cov[i][j] = E[i][j] - sum_k V[k][i] V[k][j], k ascending; cov[j][i] = the same bits
+// so the order of operations of a pair knows nothing of Q or of the pair's position. Not SPD: info = the failing column + 1 and every
+// output NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Ds, const T *As, int nquery, const T *Es,
+                                                                 T *mean, T *cov, int *info, int n, T *workspace, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV, "the five-argument form is the predictive-covariance kernel");
+    __shared__ T col[1024], va[1024], vy[1024], vq[1024];
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    const size_t nn = (size_t)n * n, qq = (size_t)nquery * nquery;
+    T *W = workspace + (size_t)blockIdx.x * (nn + (size_t)n * nquery);
+    T *V = W + nn;
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    if (mean)
+        for (int i = t; i < n; i += GL_THREADS) va[i] = Ds[k_mat * n + i];
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        if (mean)
+            for (int j = t; j < nquery; j += GL_THREADS) mean[k_mat * nquery + j] = nan_of<T>();
+        if (cov)
+            for (size_t e = t; e < qq; e += GL_THREADS) cov[k_mat * qq + e] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+        const T ajj = (T)1 / W[(size_t)j * n + j];
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+        __syncthreads();
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+            W[(size_t)j * n + i] = -s * ajj;
+        }
+        if (t == 0) W[(size_t)j * n + j] = ajj;
+        __syncthreads();
+    }
+    if (mean) {  // block-uniform
+        // y = L^-1 d: (L^-1)_kj sits at W[j*n + k]
+        for (int k = t; k < n; k += GL_THREADS) {
+            T s = 0;
+            for (int j = 0; j <= k; ++j) s += W[(size_t)j * n + k] * va[j];
+            vy[k] = s;
+        }
+        __syncthreads();
+        // alpha_i = column i of L^-1 against y; it takes the place of d
+        for (int i = t; i < n; i += GL_THREADS) {
+            T a = 0;
+            for (int k = i; k < n; ++k) a += W[(size_t)i * n + k] * vy[k];
+            va[i] = a;
+        }
+        __syncthreads();
+    }
+    for (int j = 0; j < nquery; ++j) {
+        const size_t out = k_mat * nquery + j;
+        const T *a = As + out * n;
+        for (int i = t; i < n; i += GL_THREADS) vq[i] = a[i];
+        __syncthreads();
+        T sm = 0;
+        for (int k = t; k < n; k += GL_THREADS) {
+            if (cov) {  // V[k][j] = row k of L^-1 against a
+                T s = 0;
+                for (int i = 0; i <= k; ++i) s += W[(size_t)i * n + k] * vq[i];
+                V[(size_t)j * n + k] = s;
+            }
+            if (mean) sm += vq[k] * va[k];
+        }
+        if (mean) {  // block-uniform: the block sum on the fixed tree of the prediction form
+            vy[t] = sm;
+            __syncthreads();
+            for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+                if (t < off) vy[t] += vy[t + off];
+                __syncthreads();
+            }
+            if (t == 0) mean[out] = vy[0];
+        }
+        __syncthreads();  // the next query overwrites vq and vy; after the last one, V is complete for every thread
+    }
+    if (cov) {  // block-uniform
+        const T *E = Es ? Es + k_mat * qq : nullptr;
+        T *C = cov + k_mat * qq;
+        for (size_t e = t; e < qq; e += GL_THREADS) {
+            const int j = (int)(e / nquery), i = (int)(e - (size_t)j * nquery);
+            if (i < j) continue;
+            const T *vi = V + (size_t)i * n, *vj = V + (size_t)j * n;
+            T s = 0;
+            for (int k = 0; k < n; ++k) s += vi[k] * vj[k];
+            const T v = (E ? E[e] : (T)0) - s;
+            C[e] = v;
+            C[(size_t)i * nquery + j] = v;
+        }
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_predict_cov_global(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *cov,
+                                     size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk, each with its n x Q block V, fit the blocked-path workspace cap (launch_predict_global)
+    const size_t per = (size_t)n * ((size_t)n + (size_t)nquery);
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Bs, Cs, Ds, As,
+                           nquery, Es, mean, cov, info, n, ws, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_predict_cov_global<double>(int, int, const double *, const double *, const double *, const double *,
+                                                      const double *, double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_predict_cov_global<float>(int, int, const float *, const float *, const float *, const float *, const float *,
+                                                     float *, float *, size_t, int *, hipStream_t);
+
+const char *name_predict_cov_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true>" : "matinv_chol_global<float, true, true, true, true>";
+}
+
 }  // namespace matinv

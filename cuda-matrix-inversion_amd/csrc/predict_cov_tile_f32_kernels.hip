@@ -1,0 +1,10 @@
+// predict_cov_tile_f32_kernels.hip -- fp32 instantiation of the one-wavefront GP predictive-covariance tile kernels
+// (predict_cov_tile_impl.hpp); a translation unit of its own so that the two precisions compile in parallel
+#include "predict_cov_tile_impl.hpp"
+
+namespace matinv {
+
+template hipError_t launch_predict_cov_tile<float>(int, int, const float *, const float *, const float *, const float *, const float *,
+                                                   float *, float *, size_t, int *, hipStream_t);
+
+}  // namespace matinv

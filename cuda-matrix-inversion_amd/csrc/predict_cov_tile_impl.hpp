@@ -1,44 +1,42 @@
-// predict_tile_impl.hpp (instantiated by predict_tile_kernels.hip for f64 and predict_tile_f32_kernels.hip for f32) -- GP prediction at
-// many query points per covariance matrix on the MFMA tile layout, n <= 96. With M = B + diag c (c optional), K = M^-1, alpha = K d and Q
-// query points per matrix, a_j the cross-covariance vector of query j and e_j its prior variance:
-//     mean[j] = a_j^T alpha      var[j] = e_j - a_j^T K a_j
-// The load, the PanelSolve pipeline and the block-step loop are those of logml_grad_tile_body (logml_grad_tile_impl.hpp), copied once
-// more so that the inverse, the LOO and the gradient kernels compile to what they compiled to before. The sweep ends with W = -M^-1 in
-// the lower tiles (diagonal tiles complete); the epilogue folds alpha = -W d out of the registers as the gradient epilogue does, then
-// takes the queries in groups of 16: a group is an N x 16 right-hand side, so T = W A is MFMA work, and neither M nor its inverse is
-// ever stored.
-// HBM traffic per matrix: n^2 / 2 + 2 n + Q (n + 1) elements in, 2 Q out.
+// predict_cov_tile_impl.hpp (instantiated by predict_cov_tile_kernels.hip for f64 and predict_cov_tile_f32_kernels.hip for f32) -- the
+// joint predictive covariance between a GP's query points on the MFMA tile layout, n <= 96. With M = B + diag c (c optional), K = M^-1,
+// alpha = K d and Q query points per matrix, a_i the cross-covariance vector of query i and E the Q x Q prior covariance of the queries:
+//     mean[i] = a_i^T alpha      cov[i][j] = E[i][j] - a_i^T K a_j
+// The load, the PanelSolve pipeline, the block-step loop and the alpha step are those of predict_tile_body (predict_tile_impl.hpp), copied
+// once more so that every earlier kernel compiles to what it compiled to before. The sweep ends with W = -M^-1 in the lower tiles; the
+// epilogue takes the queries in groups of 16 as the prediction form does, and for every column group g builds T_g = W A_g once and
+// multiplies it with A_g'^T for every row group g' >= g on the MFMA unit: only the lower block triangle is computed, the upper one is a
+// copy of its bits, and neither M nor its inverse is ever stored.
+// HBM traffic per matrix: n^2 / 2 + 2 n + 16 n G (G + 1) / 2 + Q^2 / 2 elements in (G = ceil(Q / 16)), Q^2 + Q out.
 // A non-positive (or NaN) pivot makes info = its column + 1 (PanelSolve::binfo) and every output NaN: no fallback launch.
 //
-// The kernels are the prediction forms of the SPD inversion kernels whose sweep they run: overloads of matinv_spd_tile_f64 / _f32 with
-// three more trailing template arguments ("Prediction at many query points", says why).
+// The kernels are the covariance forms of the SPD inversion kernels whose sweep they run: overloads of matinv_spd_tile_f64 / _f32 with
+// four more trailing template arguments ("Joint predictive covariance", says why).
 #pragma once
-#include "logml_grad_tile_impl.hpp"  // dpp_row_sum16, the launch bounds of the gradient forms
+#include "predict_tile_impl.hpp"  // predict_qstride, predict_tile_grid, the launch bounds of the prediction forms
 
 namespace matinv {
 
-// Row stride of the staged query vectors in LDS: N + 1, so that the 16 lanes of a q group, which read 16 different vectors at one row
-// index, fall into 16 different banks (odd stride) instead of one.
-constexpr int predict_qstride(int n_pad) { return n_pad + 1; }
-
 // Epilogue layout (lane l = 16 q + c; the lane holds W[16 ti + trow(r, q)][16 tj + c] in acc[ti][tj][r], tj <= ti):
-//   LDS: panel[4 N] (the sweep's; d and the row part of W d during the alpha step, then the panel of each block step again),
-//        al[N] = alpha, aq[16 (N + 1)] = the 16 query vectors of the current group, vector j at aq + j (N + 1), zero beyond n and
-//        beyond Q.
-//   alpha : as in logml_grad_tile_body -- row part over the 16 c lanes by DPP, mirror part over the four q groups. Skipped (and d not
-//           read) when mean is not asked for.
-//   T = W A, N x 16, one vec4 per tile row: for every real block step kb the four columns of W that block holds go to the LDS panel
-//           (spd_panel_to_lds writes all N rows of them, the rows above the diagonal tile by symmetry), lane (q, c) takes
-//           W[16 ti + c][pivot q] as the A operand and a_c[pivot q] as the B operand: 4 NT^2 MFMAs per group. Lane (q, c) then holds
-//           T[16 ti + trow(r, q)][query c], i.e. only values of ITS query c.
-//   var   : s = sum_ti sum_r T[ti][r] a_c[16 ti + trow(r, q)] in four chains by register r, ((p0 + p1) + (p2 + p3)), the four q groups
-//           by two __shfl_xor (16, 32); var = e + s because W = -K. No reduction over the 16 c lanes: each is another query.
-//   mean  : the same reduction of a_c[row] alpha[row].
-//   Lane group q = 0 stores the 16 results as one segment, predicated on j < Q. The order of operations for query j knows nothing of
-//   batch, grid, Q or the position of j in its group (every lane column of an MFMA is computed alike).
+//   LDS: panel[4 N], al[N] = alpha, aq[16 (N + 1)] = the 16 query vectors of ONE group, as in predict_tile_body.
+//   alpha, mean : the operations of predict_tile_body in its order, so mean carries the bits matinv_predict_batched returns.
+//   for every column group g:
+//     stage A_g; mean of its 16 queries; T_g = W A_g as in predict_tile_body: lane (q, c) holds T_g[16 ti + trow(r, q)][c] in tq[ti][r].
+//     for every row group g' >= g (g' = g: A_g is staged already; g' > g: the same buffer is restaged, T_g lives in registers):
+//       C = A_g'^T T_g, 16 x 16: for fixed (ti, r) the four lane groups q hold rows 16 ti + trow(r, q) of T_g, one per q -- a K-slab
+//           of four rows in the lane layout of the MFMA's B operand as it stands; the A operand of the slab is the same four rows of
+//           A_g', lane (q, c) reading a_c[16 ti + trow(r, q)] of group g'. 4 NT MFMAs in the order (ti, r), no shuffle. Lane (q, c)
+//           ends with C[r] = -a_i^T K a_j, i = 16 g' + trow(r, q), j = 16 g + c, because trow is the MFMA's D-row map.
+//       cov[i][j] = E[i][j] + C[r], stored at (i, j) and, the same bits, at (j, i); in the diagonal block only lanes with i >= j store.
+//       Stores are predicated on i, j < Q; only the lower triangle of E is read. The block has consecutive lanes on consecutive j,
+//       which is the order of the (j, i) store; E and the (i, j) store want them on consecutive i, so E comes in and the block goes
+//       out transposed through a 16 x 17 tile in the query buffer (two LDS round trips of four elements a lane): every global access
+//       of the epilogue is then a run of 16 consecutive elements.
+//   The order of operations for (i, j), i >= j, knows nothing of batch, grid, Q, the groups of i and j or their lanes (every row and
+//   every column of an MFMA is computed alike).
 template <class T, int NT, bool FULL>
-__device__ __forceinline__ void predict_tile_body(const T *Bs, const T *Cs, const T *Ds, const T *As, int nquery, const T *Es, T *mean,
-                                                  T *var, int *info, int n_rt, unsigned batch, T *panel, T *al, T *aq)
+__device__ __forceinline__ void predict_cov_tile_body(const T *Bs, const T *Cs, const T *Ds, const T *As, int nquery, const T *Es,
+                                                      T *mean, T *cov, int *info, int n_rt, unsigned batch, T *panel, T *al, T *aq)
 {
     typedef TileGeo<T> G;
     typedef typename G::vec4 vec4;
@@ -203,6 +201,8 @@ __device__ __forceinline__ void predict_tile_body(const T *Bs, const T *Cs, cons
             }
         }
         const int ngroups = (nquery + 15) >> 4;
+        T *const covm = cov ? cov + (size_t)mat * nquery * nquery : nullptr;
+        const T *const Em = (cov && Es) ? Es + (size_t)mat * nquery * nquery : nullptr;
         for (int g = 0; g < ngroups; ++g) {
             // lane coordinates and n opaque once per group: otherwise the offsets of the staging loads and of the LDS reads are hoisted
             // out of this loop and the allocator spills them beside the accumulators (as in the loop over p of logml_grad_tile_body)
@@ -222,8 +222,21 @@ __device__ __forceinline__ void predict_tile_body(const T *Bs, const T *Cs, cons
             }
             wave_lds_sync();
             const T *const ac = aq + cg * NS;  // the vector of this lane's query
-            if (var) {                         // wave-uniform
+            if (mean) {                        // wave-uniform; before the row groups restage aq
                 T part[4] = {(T)0, (T)0, (T)0, (T)0};
+#pragma unroll
+                for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 16 * ti + G::trow(r, qg);
+                        part[r] = fma_t(ac[row], al[row], part[r]);
+                    }
+                T s = (part[0] + part[1]) + (part[2] + part[3]);
+                s += __shfl_xor(s, 16);
+                s += __shfl_xor(s, 32);
+                if (qg == 0 && cg < left) mean[first + cg] = ok ? s : nan_of<T>();
+            }
+            if (cov) {  // wave-uniform
                 vec4 tq[NT];
 #pragma unroll
                 for (int ti = 0; ti < NT; ++ti)
@@ -241,31 +254,64 @@ __device__ __forceinline__ void predict_tile_body(const T *Bs, const T *Cs, cons
 #pragma unroll
                     for (int ti = 0; ti < NT; ++ti) tq[ti] = G::mfma(panel[(16 * ti + cg) * 4 + qg], b, tq[ti]);
                 }
+                const int j = 16 * g + cg;  // this lane's column of cov
+                for (int gp = g; gp < ngroups; ++gp) {
+                    // opaque once per row group, for the reason given at the loop over g
+                    int nr = ng, lr = lg, qr = qg, cr = cg;
+                    if (!FULL) asm volatile("" : "+s"(nr));
+                    asm volatile("" : "+v"(lr), "+v"(qr), "+v"(cr));
+                    if (gp > g) {  // wave-uniform: the row group's vectors take the place of the column group's
+                        const int leftr = nquery - 16 * gp;
+                        const T *Ar = As + ((size_t)mat * nquery + 16 * (size_t)gp) * nr;
+                        wave_lds_sync();  // the previous block's reads of aq
 #pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
+                        for (int k = 0; k < N / 4; ++k) {
+                            const int e = lr + 64 * k, jj = e / N, i = e - jj * N;
+                            const bool in = (FULL || i < nr) && jj < leftr;
+                            aq[jj * NS + i] = in ? Ar[(unsigned)(jj * nr + i)] : (T)0;
+                        }
+                        wave_lds_sync();
+                    }
+                    const T *const ar = aq + cr * NS;  // as the A operand lane (q, c) supplies row c of A_g'^T
+                    vec4 cb;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) part[r] = fma_t(tq[ti][r], ac[16 * ti + G::trow(r, qg)], part[r]);
-                T s = (part[0] + part[1]) + (part[2] + part[3]);
-                s += __shfl_xor(s, 16);
-                s += __shfl_xor(s, 32);
-                if (qg == 0 && cg < left) {
-                    const T e = Es ? Es[first + cg] : (T)0;
-                    var[first + cg] = ok ? e + s : nan_of<T>();
-                }
-            }
-            if (mean) {  // wave-uniform
-                T part[4] = {(T)0, (T)0, (T)0, (T)0};
+                    for (int r = 0; r < 4; ++r) cb[r] = (T)0;
 #pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
+                    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) cb = G::mfma(ar[16 * ti + G::trow(r, qr)], tq[ti][r], cb);
+                    // E and the lower store want consecutive lanes on consecutive i (element (i, j) at j Q + i), the block has them on
+                    // consecutive j: both go through a 16 x 16 tile in the query buffer, which is free once the MFMAs have read it
+                    // (the next row group, or the next column group, restages it). In the transposed layout lane (q, c) serves
+                    // i = 16 g' + c, j = 16 g + trow(r, q).
+                    constexpr int TS = 17;  // 16 (N + 1) >= 16 * 17 elements
+                    const int it = 16 * gp + cr;
+                    wave_lds_sync();  // the A operands have been read
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int row = 16 * ti + G::trow(r, qg);
-                        part[r] = fma_t(ac[row], al[row], part[r]);
+                        const int jl = G::trow(r, qr), jt = 16 * g + jl;
+                        const bool in = it < nquery && jt < nquery && it >= jt;
+                        aq[jl * TS + cr] = (Em && in) ? Em[(unsigned)jt * (unsigned)nquery + (unsigned)it] : (T)0;
                     }
-                T s = (part[0] + part[1]) + (part[2] + part[3]);
-                s += __shfl_xor(s, 16);
-                s += __shfl_xor(s, 32);
-                if (qg == 0 && cg < left) mean[first + cg] = ok ? s : nan_of<T>();
+                    wave_lds_sync();
+                    T v[4];  // E[i][j] + C in the block's layout: i by (r, q), j by c
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = ok ? aq[cr * TS + G::trow(r, qr)] + cb[r] : nan_of<T>();
+                    wave_lds_sync();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int il = G::trow(r, qr), i = 16 * gp + il;  // i >= j in every block below the diagonal ones
+                        aq[il * TS + cr] = v[r];
+                        if (i < nquery && j < nquery && i >= j) covm[(unsigned)i * (unsigned)nquery + (unsigned)j] = v[r];  // the mirror
+                    }
+                    wave_lds_sync();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int jl = G::trow(r, qr), jt = 16 * g + jl;
+                        const T w = aq[cr * TS + jl];  // the bits of (i, j) = (it, jt)
+                        if (it < nquery && jt < nquery && it >= jt) covm[(unsigned)jt * (unsigned)nquery + (unsigned)it] = w;
+                    }
+                }
             }
         }
         int code = binfo;
@@ -281,55 +327,50 @@ __device__ __forceinline__ void predict_tile_body(const T *Bs, const T *Cs, cons
     }
 }
 
-// The prediction forms of matinv_spd_tile_f64 / matinv_spd_tile_f32 (tile_impl.hpp): the same names with a third, a fourth and a fifth
-// template argument, the launch bounds of the gradient forms for the same NT (logml_grad_tile_impl.hpp) -- except the full fp64 6 x 6
-// form, which spills under them beside its NT more accumulators (170 registers at two waves per SIMD; still 20 with T built one tile
-// row at a time: profiles/predict_kernel_registers.txt) and takes one wave per SIMD like the ragged one, and no scratch.
-constexpr int predict_f64_waves(int nt, bool full) { return nt >= 6 ? 1 : logml_grad_f64_waves(nt, full); }
-constexpr int predict_f32_waves(int nt, bool full) { return logml_grad_f32_waves(nt, full); }
+// The covariance forms of matinv_spd_tile_f64 / matinv_spd_tile_f32 (tile_impl.hpp): the same names with a third to a sixth template
+// argument. Launch bounds: those of the prediction forms for the same NT (predict_tile_impl.hpp), one wave per SIMD fewer where a form
+// spills under them (profiles/predict_cov_kernel_registers.txt); no form uses scratch.
+constexpr int predict_cov_f64_waves(int nt, bool full) { return predict_f64_waves(nt, full); }
+constexpr int predict_cov_f32_waves(int nt, bool full) { return predict_f32_waves(nt, full); }
 
-template <int NT, bool FULL, bool LOO, bool GRAD, bool PREDICT>
-__global__ __launch_bounds__(64, predict_f64_waves(NT, FULL)) void matinv_spd_tile_f64(const double *Bs, const double *Cs, const double *Ds,
-                                                                                              const double *As, int nquery, const double *Es,
-                                                                                              double *mean, double *var, int *info, int n_rt,
-                                                                                              unsigned batch)
+template <int NT, bool FULL, bool LOO, bool GRAD, bool PREDICT, bool COV>
+__global__ __launch_bounds__(64, predict_cov_f64_waves(NT, FULL)) void matinv_spd_tile_f64(const double *Bs, const double *Cs,
+                                                                                                  const double *Ds, const double *As, int nquery,
+                                                                                                  const double *Es, double *mean, double *cov,
+                                                                                                  int *info, int n_rt, unsigned batch)
 {
-    static_assert(LOO && GRAD && PREDICT, "the five-argument form is the prediction kernel");
+    static_assert(LOO && GRAD && PREDICT && COV, "the six-argument form is the predictive-covariance kernel");
     __shared__ __attribute__((aligned(16))) double panel[16 * NT * 4];
     __shared__ double al[16 * NT], aq[16 * predict_qstride(16 * NT)];
-    predict_tile_body<double, NT, FULL>(Bs, Cs, Ds, As, nquery, Es, mean, var, info, n_rt, batch, panel, al, aq);
+    predict_cov_tile_body<double, NT, FULL>(Bs, Cs, Ds, As, nquery, Es, mean, cov, info, n_rt, batch, panel, al, aq);
 }
 
-template <int NT, bool FULL, bool LOO, bool GRAD, bool PREDICT>
-__global__ __launch_bounds__(64, predict_f32_waves(NT, FULL)) void matinv_spd_tile_f32(const float *Bs, const float *Cs, const float *Ds,
-                                                                                              const float *As, int nquery, const float *Es,
-                                                                                              float *mean, float *var, int *info, int n_rt,
-                                                                                              unsigned batch)
+template <int NT, bool FULL, bool LOO, bool GRAD, bool PREDICT, bool COV>
+__global__ __launch_bounds__(64, predict_cov_f32_waves(NT, FULL)) void matinv_spd_tile_f32(const float *Bs, const float *Cs, const float *Ds,
+                                                                                                  const float *As, int nquery, const float *Es,
+                                                                                                  float *mean, float *cov, int *info, int n_rt,
+                                                                                                  unsigned batch)
 {
-    static_assert(LOO && GRAD && PREDICT, "the five-argument form is the prediction kernel");
+    static_assert(LOO && GRAD && PREDICT && COV, "the six-argument form is the predictive-covariance kernel");
     __shared__ __attribute__((aligned(16))) float panel[16 * NT * 4];
     __shared__ float al[16 * NT], aq[16 * predict_qstride(16 * NT)];
-    predict_tile_body<float, NT, FULL>(Bs, Cs, Ds, As, nquery, Es, mean, var, info, n_rt, batch, panel, al, aq);
+    predict_cov_tile_body<float, NT, FULL>(Bs, Cs, Ds, As, nquery, Es, mean, cov, info, n_rt, batch, panel, al, aq);
 }
 
-// The grid of the prediction forms and of the covariance forms built on them (predict_cov_tile_impl.hpp): one place, so that what
-// tests/test_grid_stride_cpu.py reads here holds for both launch sites.
-inline unsigned predict_tile_grid(size_t batch) { return tile_grid(batch, 12u); }
-
 template <class T>
-hipError_t launch_predict_tile(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *var,
-                               size_t batch, int *info, hipStream_t stream)
+hipError_t launch_predict_cov_tile(int n, int nquery, const T *Bs, const T *Cs, const T *Ds, const T *As, const T *Es, T *mean, T *cov,
+                                   size_t batch, int *info, hipStream_t stream)
 {
-    if (!predict_tile_supports(n)) return hipErrorInvalidValue;
+    if (!predict_cov_tile_supports(n)) return hipErrorInvalidValue;
     if (batch == 0) return hipSuccess;
-    const unsigned grid = predict_tile_grid(batch), b = (unsigned)batch;
+    const unsigned grid = predict_tile_grid(batch), b = (unsigned)batch;  // 256 * 12 workgroups a round (predict_tile_impl.hpp)
     with_tile<1, 6>(tile_shape(n), [&](auto NT, auto FULL) {
         if constexpr (sizeof(T) == 8)
-            hipLaunchKernelGGL((matinv_spd_tile_f64<NT, FULL, true, true, true>), dim3(grid), dim3(64), 0, stream, Bs, Cs, Ds, As, nquery, Es,
-                               mean, var, info, n, b);
+            hipLaunchKernelGGL((matinv_spd_tile_f64<NT, FULL, true, true, true, true>), dim3(grid), dim3(64), 0, stream, Bs, Cs, Ds, As, nquery,
+                               Es, mean, cov, info, n, b);
         else
-            hipLaunchKernelGGL((matinv_spd_tile_f32<NT, FULL, true, true, true>), dim3(grid), dim3(64), 0, stream, Bs, Cs, Ds, As, nquery, Es,
-                               mean, var, info, n, b);
+            hipLaunchKernelGGL((matinv_spd_tile_f32<NT, FULL, true, true, true, true>), dim3(grid), dim3(64), 0, stream, Bs, Cs, Ds, As, nquery,
+                               Es, mean, cov, info, n, b);
     });
     return hipGetLastError();
 }

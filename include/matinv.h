@@ -267,6 +267,33 @@ const char *matinv_predict_kernel_name(int dtype, int n);
 int matinv_predict_batched_host(int dtype, int n, int nquery, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
                                 const void *hEs, void *hMean, void *hVar, size_t batch, int *info);
 
+/* The joint predictive covariance between the nquery query points of a covariance matrix, device-resident. With M, K, alpha and a_ki as in
+ * matinv_predict_batched and E_k the nquery x nquery prior covariance between the queries of matrix k:
+ *   mean[k*nquery + i]                      = a_ki^T alpha_k                   the predictive mean
+ *   cov[k*nquery^2 + j*nquery + i]          = E_k[i][j] - a_ki^T K_k a_kj      nquery x nquery per matrix, column-major
+ * dBs, dCs, dDs, dAs as in matinv_predict_batched (only the lower triangle of B read; dCs may be NULL). dEs: batch*nquery^2 elements,
+ * column-major per matrix, of which only the lower triangle is read (element (i, j), i >= j, at j*nquery + i), or NULL (E = 0). dCov:
+ * batch*nquery^2 elements, BOTH triangles written: the lower element (i >= j) is computed and the upper one is a copy of its bits, so the
+ * result is exactly symmetric. dMean: batch*nquery elements. Either output may be NULL (both NULL: MATINV_ERR_ARG), and which of them is
+ * requested does not change a bit of the other. dDs is read only with dMean, dEs only with dCov. 1 <= nquery <= 1024 (beyond:
+ * MATINV_ERR_UNSUPPORTED). cov is not clamped or regularised. mean carries the same bits as matinv_predict_batched returns for the
+ * same inputs; the diagonal of cov equals its var only to rounding, because it is summed on the MFMA unit. No input is modified
+ * (outputs must not overlap inputs); neither M nor its inverse is written to caller memory. Bit for bit, mean[k, i] depends on matrix
+ * k and query i alone, and cov[k, i, j] with i >= j on matrix k, a_ki, a_kj and E_k[i][j] alone -- not on batch, nquery or the positions
+ * of i and j among the queries, as long as i stays the later of the two (swapping two queries may change the last bits). dInfo
+ * (optional): 0, or the 1-based column of the first non-positive (or NaN) pivot -- all nquery^2 + nquery outputs of that matrix are
+ * then NaN. n <= 96: the covariance form of the one-wavefront SPD tile sweep, a 16 x 16 block of cov per pair of query groups on the
+ * MFMA unit (n^2/2 + 2n + 16 n G (G + 1) / 2 + nquery^2 / 2 elements read with G = ceil(nquery / 16), nquery^2 + nquery written).
+ * Beyond, to n = 1024: the covariance form of the global-memory Cholesky kernel on a working copy of n (n + nquery) elements per matrix
+ * in library scratch. Asynchronous, no host synchronisation. */
+int matinv_predict_cov_batched(int dtype, int n, int nquery, const void *dBs, const void *dCs, const void *dDs, const void *dAs,
+                               const void *dEs, void *dMean, void *dCov, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a predictive-covariance request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_predict_cov_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, hEs, `info` and each output optional; hDs is read only with hMean, hEs only with hCov). Synchronous. */
+int matinv_predict_cov_batched_host(int dtype, int n, int nquery, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
+                                    const void *hEs, void *hMean, void *hCov, size_t batch, int *info);
+
 /* Host-pointer convenience used by the reference-named *_gpu wrappers: allocate, H2D, invert, D2H, free.
  * `info` is an optional host int[batch]. Synchronous. */
 int matinv_inverse_batched_host(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info);
