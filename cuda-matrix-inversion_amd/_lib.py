@@ -45,6 +45,7 @@ NATIVE_NAMES = [
     "matinv_logml_grad_batched", "matinv_logml_grad_kernel_name", "matinv_logml_grad_batched_host",
     "matinv_predict_batched", "matinv_predict_kernel_name", "matinv_predict_batched_host",
     "matinv_predict_cov_batched", "matinv_predict_cov_kernel_name", "matinv_predict_cov_batched_host",
+    "matinv_loo_grad_batched", "matinv_loo_grad_kernel_name", "matinv_loo_grad_batched_host",
 ]
 GJ_NATURAL_FIRST, GJ_PIVOT, GJ_ADAPTIVE = 0, 1, 2
 
@@ -128,6 +129,12 @@ def lib() -> ctypes.CDLL:
     L.matinv_predict_cov_kernel_name.argtypes = [ci, ci]
     L.matinv_predict_cov_batched_host.restype = ci
     L.matinv_predict_cov_batched_host.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.matinv_loo_grad_batched.restype = ci
+    L.matinv_loo_grad_batched.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    L.matinv_loo_grad_kernel_name.restype = ctypes.c_char_p
+    L.matinv_loo_grad_kernel_name.argtypes = [ci, ci]
+    L.matinv_loo_grad_batched_host.restype = ci
+    L.matinv_loo_grad_batched_host.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.matinv_select_kernel.restype = ci
     L.matinv_select_kernel.argtypes = [ci, ci, ci]
     L.matinv_kernel_name.restype = ctypes.c_char_p

@@ -501,6 +501,98 @@ def logml_grad_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_logml_grad_kernel_name(code, n).decode()
 
 
+_LOO_GRAD_OUTPUTS = ("grad", "gradc", "logpl")
+
+
+def loo_grad_batched(n, Bs, Cs, Ds, dMs, grad=None, gradc=None, logpl=None, batchSize=None, info=None, want=("grad",)):
+    """Gradients of the GP leave-one-out log pseudo-likelihood on device tensors (matinv_loo_grad_batched; asynchronous on torch's current
+    stream). With M_k = B_k + diag c_k, K = M^-1, alpha = K d, kappa_i = K_ii, b_i = alpha_i / kappa_i, beta = K b,
+    s_i = (1 + alpha_i^2 / kappa_i) / kappa_i and G = 1/2 (alpha beta^T + beta alpha^T) - 1/2 K diag(s) K:
+    grad[k, p] = sum_ij G_ij dM_p[i, j] for the P symmetric derivative matrices of matrix k (dMs: batchSize*P*n*n elements, matrix (k, p)
+    at (k*P + p)*n*n, column-major, lower triangle read), gradc[k, i] = G_ii (the derivative w.r.t. c_i), logpl[k] = the pseudo-likelihood
+    itself, as loo_batched returns it.
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one. Cs may be None (M = B),
+    dMs may be None when grad is not asked for. P is dMs.numel() // (batchSize*n*n). Only the lower triangles of B and dM are read and no
+    input is modified. Returns (grad, gradc, logpl), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Ds, dMs, grad, gradc, logpl, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    unknown = set(want) - set(_LOO_GRAD_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_LOO_GRAD_OUTPUTS}")
+    if grad is None and gradc is None and logpl is None and not want:
+        raise ValueError("no output requested")
+    nparam = 0
+    if grad is not None or "grad" in want:
+        if dMs is None:
+            raise ValueError("grad needs the derivative matrices dMs")
+        nparam = dMs.numel() // (batchSize * n * n) if batchSize else 0
+        if batchSize and (nparam < 1 or dMs.numel() < batchSize * nparam * n * n):
+            raise ValueError("dMs needs batchSize*P*n*n elements, P >= 1")
+        if grad is None:
+            grad = torch.empty(batchSize * nparam, dtype=Bs.dtype, device=Bs.device)
+    if gradc is None and "gradc" in want:
+        gradc = torch.empty(batchSize * n, dtype=Bs.dtype, device=Bs.device)
+    if logpl is None and "logpl" in want:
+        logpl = torch.empty(batchSize, dtype=Bs.dtype, device=Bs.device)
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, dMs, grad, gradc, logpl)):
+        raise TypeError("Bs, Cs, Ds, dMs, grad, gradc and logpl must have one dtype")
+    if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds, gradc)) or (grad is not None and grad.numel() < batchSize * nparam) \
+            or (logpl is not None and logpl.numel() < batchSize):
+        raise ValueError("Cs, Ds and gradc need batchSize*n elements, grad batchSize*P, logpl batchSize")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_loo_grad_batched(
+            _torch_dtype_code(Bs), n, nparam, p(Bs), p(Cs), p(Ds), p(dMs) if grad is not None else None, p(grad), p(gradc), p(logpl),
+            batchSize, p(info), _stream_ptr(Bs)))
+    return grad, gradc, logpl
+
+
+def loo_grad_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray, dMs, want=_LOO_GRAD_OUTPUTS):
+    """matinv_loo_grad_batched_host on numpy batches (packed; Cs may be None, dMs may be None without "grad" in want): returns
+    (grad, gradc, logpl, info), None for the outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Ds = np.ascontiguousarray(Ds)
+    Cs = None if Cs is None else np.ascontiguousarray(Cs)
+    dMs = None if dMs is None else np.ascontiguousarray(dMs)
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, dMs)):
+        raise TypeError("Bs, Cs, Ds and dMs must have one dtype")
+    unknown = set(want) - set(_LOO_GRAD_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_LOO_GRAD_OUTPUTS}")
+    batch = Bs.size // (n * n)
+    if Ds.size < batch * n or (Cs is not None and Cs.size < batch * n):
+        raise ValueError("Cs and Ds smaller than batch*n")
+    nparam = 0
+    grad = gradc = logpl = None
+    if "grad" in want:
+        if dMs is None:
+            raise ValueError("grad needs the derivative matrices dMs")
+        nparam = dMs.size // (batch * n * n) if batch else 0
+        if batch and nparam < 1:
+            raise ValueError("dMs needs batch*P*n*n elements, P >= 1")
+        grad = np.empty(batch * nparam, dtype=Bs.dtype)
+    if "gradc" in want:
+        gradc = np.empty(batch * n, dtype=Bs.dtype)
+    if "logpl" in want:
+        logpl = np.empty(batch, dtype=Bs.dtype)
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_loo_grad_batched_host(
+        _np_dtype_code(Bs.dtype), n, nparam, p(Bs), p(Cs), p(Ds), p(dMs) if grad is not None else None, p(grad), p(gradc), p(logpl), batch,
+        p(info)))
+    return grad, gradc, logpl, info
+
+
+def loo_grad_kernel_name(dtype, n: int) -> str:
+    """matinv_loo_grad_kernel_name: the kernel a LOO-gradient request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_loo_grad_kernel_name(code, n).decode()
+
+
 _PREDICT_OUTPUTS = ("mean", "var")
 
 

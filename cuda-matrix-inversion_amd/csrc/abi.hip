@@ -1013,6 +1013,73 @@ int logml_grad_host(int n, int nparam, const void *hBs, const void *hCs, const v
     return MATINV_OK;
 }
 
+// ---- gradients of the batched GP leave-one-out log pseudo-likelihood (matinv_loo_grad_batched) -----------------------------------------
+int loo_grad_check_args(int dtype, int n, int nparam, const void *dBs, const void *dDs, const void *dDMs, const void *dGrad,
+                        const void *dGradC, const void *dLogPL, size_t batch)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (nparam < 0) return fail(MATINV_ERR_ARG, "nparam must be >= 0 (got %d)", nparam);
+    if (!dBs || !dDs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dGrad && !dGradC && !dLogPL) return fail(MATINV_ERR_ARG, "no output requested (grad, gradc and logpl are all null)");
+    if (dGrad && nparam < 1) return fail(MATINV_ERR_ARG, "grad requested with nparam = 0");
+    if (dGrad && !dDMs) return fail(MATINV_ERR_ARG, "grad requested without derivative matrices (dDMs is null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    return MATINV_OK;
+}
+
+// n <= 96: the LOO-gradient form of the one-wavefront SPD sweep. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
+template <class T>
+int loo_grad_dispatch(int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad, void *dGradC,
+                      void *dLogPL, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *d = static_cast<const T *>(dDs);
+    const T *dM = static_cast<const T *>(dDMs);
+    T *grad = static_cast<T *>(dGrad), *gradc = static_cast<T *>(dGradC), *logpl = static_cast<T *>(dLogPL);
+    const hipError_t e = loo_grad_tile_supports(n)
+                             ? launch_loo_grad_tile<T>(n, nparam, B, c, d, dM, grad, gradc, logpl, batch, dInfo, stream)
+                             : launch_loo_grad_global<T>(n, nparam, B, c, d, dM, grad, gradc, logpl, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "loo_grad launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int loo_grad_host(int n, int nparam, const void *hBs, const void *hCs, const void *hDs, const void *hDMs, void *hGrad, void *hGradC,
+                  void *hLogPL, size_t batch, int *info)
+{
+    const size_t vec = (size_t)n * batch, mat = vec * n, par = batch * (size_t)nparam;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dDM = nullptr, *dGrad = nullptr, *dGradC = nullptr, *dLogPL = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
+    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dDM), par * (size_t)n * n * sizeof(T));
+    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dGrad), par * sizeof(T));
+    if (e == hipSuccess && hGradC) e = staging_alloc(reinterpret_cast<void **>(&dGradC), vec * sizeof(T));
+    if (e == hipSuccess && hLogPL) e = staging_alloc(reinterpret_cast<void **>(&dLogPL), batch * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hGrad) e = hipMemcpy(dDM, hDMs, par * (size_t)n * n * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = loo_grad_dispatch<T>(n, nparam, dB, dC, dD, dDM, dGrad, dGradC, dLogPL, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hGrad) e = hipMemcpy(hGrad, dGrad, par * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hGradC) e = hipMemcpy(hGradC, dGradC, vec * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hLogPL) e = hipMemcpy(hLogPL, dLogPL, batch * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dDM), staging_free(dGrad), staging_free(dGradC), staging_free(dLogPL);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "loo_grad host<->device");
+    return MATINV_OK;
+}
+
 // ---- batched GP prediction at many query points per matrix (matinv_predict_batched) ---------------------------------------------------
 int predict_check_args(int dtype, int n, int nquery, const void *dBs, const void *dDs, const void *dAs, const void *dMean, const void *dVar,
                        size_t batch)
@@ -1545,6 +1612,31 @@ int matinv_predict_cov_batched_host(int dtype, int n, int nquery, const void *hB
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return predict_cov_host<double>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
     return predict_cov_host<float>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
+}
+
+int matinv_loo_grad_batched(int dtype, int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad,
+                            void *dGradC, void *dLogPL, size_t batch, int *dInfo, void *stream)
+{
+    int rc = loo_grad_check_args(dtype, n, nparam, dBs, dDs, dDMs, dGrad, dGradC, dLogPL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return loo_grad_dispatch<double>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dLogPL, batch, dInfo, st);
+    return loo_grad_dispatch<float>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dLogPL, batch, dInfo, st);
+}
+
+const char *matinv_loo_grad_kernel_name(int dtype, int n)
+{
+    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return loo_grad_tile_supports(n) ? name_loo_grad_tile(dtype == MATINV_F64, n) : name_loo_grad_global(dtype == MATINV_F64);
+}
+
+int matinv_loo_grad_batched_host(int dtype, int n, int nparam, const void *hBs, const void *hCs, const void *hDs, const void *hDMs,
+                                 void *hGrad, void *hGradC, void *hLogPL, size_t batch, int *info)
+{
+    int rc = loo_grad_check_args(dtype, n, nparam, hBs, hDs, hDMs, hGrad, hGradC, hLogPL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return loo_grad_host<double>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hLogPL, batch, info);
+    return loo_grad_host<float>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hLogPL, batch, info);
 }
 
 int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dDs,

@@ -402,6 +402,20 @@ hipError_t launch_predict_cov_global(int n, int nquery, const T *Bs, const T *Cs
                                      size_t batch, int *info, hipStream_t stream);
 const char *name_predict_cov_global(bool f64);
 
+// Gradients of the batched GP leave-one-out log pseudo-likelihood (matinv_loo_grad_batched): grad: batch * nparam, gradc: batch * n,
+// logpl: batch, each optional; dMs: batch * nparam symmetric n x n matrices (lower triangle read), needed with grad only.
+// (a) the LOO-gradient form of the one-wavefront SPD sweep, n <= 96 (loo_grad_tile_kernels.hip, loo_grad_tile_f32_kernels.hip)
+bool loo_grad_tile_supports(int n);
+template <class T>
+hipError_t launch_loo_grad_tile(int n, int nparam, const T *Bs, const T *Cs, const T *Ds, const T *dMs, T *grad, T *gradc, T *logpl,
+                                size_t batch, int *info, hipStream_t stream);
+const char *name_loo_grad_tile(bool f64, int n);
+// (b) the LOO-gradient form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_loo_grad_global(int n, int nparam, const T *Bs, const T *Cs, const T *Ds, const T *dMs, T *grad, T *gradc, T *logpl,
+                                  size_t batch, int *info, hipStream_t stream);
+const char *name_loo_grad_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

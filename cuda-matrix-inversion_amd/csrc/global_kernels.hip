@@ -769,4 +769,192 @@ const char *name_predict_cov_global(bool f64)
     return f64 ? "matinv_chol_global<double, true, true, true, true>" : "matinv_chol_global<float, true, true, true, true>";
 }
 
+// ---- gradients of the GP leave-one-out log pseudo-likelihood, 96 < n <= 1024 (matinv_loo_grad_batched behind loo_grad_tile_impl.hpp) -----
+// The LOO-gradient form of matinv_chol_global: one more template argument again ("Gradients of the leave-one-out
+// pseudo-likelihood"). The matrix's slice of library scratch is 2 n^2 elements: W, then H. The pipeline of the gradient form -- working
+// copy, factor, triangular inverse, alpha, the lower triangle of K = M^-1 in place -- continued:
+//     K mirrored into the upper triangle of W        (every later access runs down a column: consecutive threads, consecutive addresses)
+//     kappa_i = K_ii,  b_i = alpha_i / kappa_i,  s_i = (1 + alpha_i^2 / kappa_i) / kappa_i,  logpl on the fixed LDS tree
+//     beta = K b
+//     H_rc = sum_t s_t K_rt K_tc, r >= c, t ascending, one thread per element
+//     gradc_i = alpha_i beta_i - 1/2 H_ii
+//     grad_p = sum_{r >= c} w_rc (1/2 (alpha_r beta_c + beta_r alpha_c) - 1/2 H_rc) dM_p[r][c],  w = 1 on the diagonal, 2 below
+// with dM_p read from caller memory (lower triangle only) and grad_p summed per thread in element order, then on the fixed LDS tree.
+// Not SPD: info = the failing column + 1 and every output NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves
+// matrix first + blockIdx.x.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Ds, const T *dMs, int nparam, T *grad,
+                                                                 T *gradc, T *logpl, int *info, int n, T *workspace, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD, "the six-argument form is the leave-one-out gradient kernel");
+    __shared__ T col[1024], va[1024], vy[1024], vs[1024], vb[1024];
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    const size_t nn = (size_t)n * n;
+    T *W = workspace + (size_t)blockIdx.x * 2 * nn;
+    T *H = W + nn;
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    for (int i = t; i < n; i += GL_THREADS) va[i] = Ds[k_mat * n + i];
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        if (gradc)
+            for (int i = t; i < n; i += GL_THREADS) gradc[k_mat * n + i] = nan_of<T>();
+        if (grad)
+            for (int p = t; p < nparam; p += GL_THREADS) grad[k_mat * nparam + p] = nan_of<T>();
+        if (t == 0) {
+            if (logpl) logpl[k_mat] = nan_of<T>();
+            if (info) info[k_mat] = bad;
+        }
+        return;
+    }
+    for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+        const T ajj = (T)1 / W[(size_t)j * n + j];
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+        __syncthreads();
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+            W[(size_t)j * n + i] = -s * ajj;
+        }
+        if (t == 0) W[(size_t)j * n + j] = ajj;
+        __syncthreads();
+    }
+    // y = L^-1 d: (L^-1)_kj sits at W[j*n + k]
+    for (int k = t; k < n; k += GL_THREADS) {
+        T s = 0;
+        for (int j = 0; j <= k; ++j) s += W[(size_t)j * n + k] * va[j];
+        vy[k] = s;
+    }
+    __syncthreads();
+    // alpha_i = column i of L^-1 against y; it takes the place of d
+    for (int i = t; i < n; i += GL_THREADS) {
+        T a = 0;
+        for (int k = i; k < n; ++k) a += W[(size_t)i * n + k] * vy[k];
+        va[i] = a;
+    }
+    __syncthreads();
+    // column c of K over column c of L^-1; the columns beyond c are still those of L^-1
+    for (int c = 0; c < n; ++c) {
+        for (int k = c + t; k < n; k += GL_THREADS) col[k] = W[(size_t)c * n + k];
+        __syncthreads();
+        for (int r = c + t; r < n; r += GL_THREADS) {
+            T s = 0;
+            if (r == c) {
+                for (int k = r; k < n; ++k) s += col[k] * col[k];
+            } else {
+                for (int k = r; k < n; ++k) s += W[(size_t)r * n + k] * col[k];
+            }
+            W[(size_t)c * n + r] = s;
+        }
+        __syncthreads();
+    }
+    // the mirror: K_rc, r < c, from K_cr
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) W[e] = W[(size_t)r * n + c];
+    }
+    // kappa, b, s and the terms of logpl; b takes the place of y
+    T term = 0;
+    for (int i = t; i < n; i += GL_THREADS) {
+        const T kappa = W[(size_t)i * n + i], a = va[i];
+        const T rk = (T)1 / kappa;
+        const T b = a * rk;
+        vy[i] = b;
+        vs[i] = (a * b + (T)1) * rk;
+        term += (T)0.5 * gl_log<T>(kappa) - (T)0.5 * a * b;
+    }
+    col[t] = term;
+    __syncthreads();  // the mirror, b and s are complete as well
+    for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+        if (t < off) col[t] += col[t + off];
+        __syncthreads();
+    }
+    if (t == 0 && logpl) logpl[k_mat] = col[0] - (T)n * (T)0.91893853320467274178;
+    if (grad || gradc) {  // block-uniform
+        // beta_i = row i of K against b, read as column i
+        for (int i = t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int j = 0; j < n; ++j) s += W[(size_t)j * n + i] * vy[j];
+            vb[i] = s;
+        }
+        // H_rc, r >= c: K_rt runs down column t with the thread, K_tc is one address per column c
+        for (size_t e = t; e < nn; e += GL_THREADS) {
+            const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+            if (r < c) continue;
+            const T *kc = W + (size_t)c * n;
+            T s = 0;
+            for (int k = 0; k < n; ++k) s += vs[k] * W[(size_t)k * n + r] * kc[k];
+            H[e] = s;
+        }
+        __syncthreads();
+        if (gradc)
+            for (int i = t; i < n; i += GL_THREADS) gradc[k_mat * n + i] = va[i] * vb[i] - (T)0.5 * H[(size_t)i * n + i];
+        if (grad) {
+            for (int p = 0; p < nparam; ++p) {
+                const T *D = dMs + (k_mat * nparam + p) * nn;
+                T s = 0;
+                for (size_t e = t; e < nn; e += GL_THREADS) {
+                    const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+                    if (r < c) continue;
+                    const T g = (T)0.5 * (va[r] * vb[c] + vb[r] * va[c]) - (T)0.5 * H[e];
+                    s += (r == c ? (T)1 : (T)2) * g * D[e];
+                }
+                // block sum on a fixed tree
+                col[t] = s;
+                __syncthreads();
+                for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+                    if (t < off) col[t] += col[t + off];
+                    __syncthreads();
+                }
+                if (t == 0) grad[k_mat * nparam + p] = col[0];
+                __syncthreads();
+            }
+        }
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_loo_grad_global(int n, int nparam, const T *Bs, const T *Cs, const T *Ds, const T *dMs, T *grad, T *gradc, T *logpl,
+                                  size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk, each with its n x n block H, fit the blocked-path workspace cap (launch_loo_global)
+    const size_t per = 2 * (size_t)n * n;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Bs, Cs, Ds,
+                           dMs, nparam, grad, gradc, logpl, info, n, ws, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_loo_grad_global<double>(int, int, const double *, const double *, const double *, const double *, double *, double *,
+                                                   double *, size_t, int *, hipStream_t);
+template hipError_t launch_loo_grad_global<float>(int, int, const float *, const float *, const float *, const float *, float *, float *,
+                                                  float *, size_t, int *, hipStream_t);
+
+const char *name_loo_grad_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true>" : "matinv_chol_global<float, true, true, true, true, true>";
+}
+
 }  // namespace matinv

@@ -294,6 +294,32 @@ const char *matinv_predict_cov_kernel_name(int dtype, int n);
 int matinv_predict_cov_batched_host(int dtype, int n, int nquery, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
                                     const void *hEs, void *hMean, void *hCov, size_t batch, int *info);
 
+/* Gradients of the GP leave-one-out log pseudo-likelihood (the logpl matinv_loo_batched returns; Rasmussen & Williams 5.4.2),
+ * device-resident. With M_k = B_k + diag(c_k), K = M^-1, alpha = K d, kappa_i = K_ii and nparam symmetric derivative matrices
+ * dM_p = dM / d theta_p per matrix:
+ *   b_i = alpha_i / kappa_i,  beta = K b,  s_i = (1 + alpha_i^2 / kappa_i) / kappa_i,  H = K diag(s) K,
+ *   G = 1/2 (alpha beta^T + beta alpha^T) - 1/2 H
+ *   grad[k*nparam + p] = sum_ij G_ij dM_p[i][j]                                                  d logpl / d theta_p
+ *   gradc[k*n + i]     = G_ii = alpha_i beta_i - 1/2 sum_t s_t K_it^2                            d logpl / d c_i
+ *   logpl[k]           = sum_i (1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i) - n/2 log(2 pi)       the value itself
+ * B, c, d and dDMs as in matinv_logml_grad_batched (SPD, column-major, only the lower triangles of B and of every dM_p read; dCs may be
+ * NULL; matrix (k, p) of dDMs at offset (k*nparam + p)*n*n). dGrad: batch*nparam, dGradC: batch*n, dLogPL: batch; each may be NULL (all
+ * three NULL: MATINV_ERR_ARG), and which of them are requested does not change a bit of the others. dGrad needs nparam >= 1 and dDMs;
+ * without dGrad, nparam = 0 and dDMs = NULL are fine (dDMs is not read). No input is modified (outputs must not overlap inputs);
+ * neither M, its inverse nor H is written to caller memory; the result of matrix k depends on matrix k alone, and grad[k, p] on dM_p
+ * alone, bit for bit. dInfo (optional): 0, or the 1-based column of the first non-positive (or NaN) pivot -- every output of that
+ * matrix is then NaN. n <= 96: the LOO-gradient form of the one-wavefront SPD tile sweep, H built one tile column at a time on the MFMA
+ * unit ((nparam + 1) n^2/2 + 2n elements read, nparam + n + 1 written). Beyond, to n = 1024: the LOO-gradient form of the
+ * global-memory Cholesky kernel on a working copy of 2 n^2 elements per matrix in library scratch. Asynchronous, no host
+ * synchronisation. */
+int matinv_loo_grad_batched(int dtype, int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad,
+                            void *dGradC, void *dLogPL, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a LOO-gradient request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_loo_grad_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional; hDMs is read only with hGrad). Synchronous. */
+int matinv_loo_grad_batched_host(int dtype, int n, int nparam, const void *hBs, const void *hCs, const void *hDs, const void *hDMs,
+                                 void *hGrad, void *hGradC, void *hLogPL, size_t batch, int *info);
+
 /* Host-pointer convenience used by the reference-named *_gpu wrappers: allocate, H2D, invert, D2H, free.
  * `info` is an optional host int[batch]. Synchronous. */
 int matinv_inverse_batched_host(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info);
