@@ -756,6 +756,172 @@ def predict_cov_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_predict_cov_kernel_name(code, n).decode()
 
 
+_COLOUR_OUTPUTS = ("Y", "L")
+
+
+def colour_batched(q, Cs, Ms, Zs, Y=None, L=None, batchSize=None, info=None, want=_COLOUR_OUTPUTS, strideC=None):
+    """Lower Cholesky factors of batched SPD matrices and samples coloured by them on device tensors (matinv_colour_batched; asynchronous
+    on torch's current stream):  C_k = L_k L_k^T,  Y_k[:, s] = m_k + L_k z_ks.  Cs: matrix k is q x q, column-major, at element
+    k*strideC (default q*q), only the lower triangle read. Ms: batchSize*q elements or None (m = 0). Zs: batchSize*S*q elements, sample s
+    of matrix k a run of q elements; S is Zs.numel() // (batchSize*q). Y has the layout of Zs; L is batchSize*q*q, column-major, with the
+    strict upper triangle written as zeros.
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one. Zs may be None when Y is
+    not asked for. No input is modified and the library draws no random numbers: Zs is the caller's. Not positive definite: info = the
+    1-based column of the first non-positive pivot and every requested output of that matrix NaN; there is no jitter.
+    Returns (Y, L), None for what was not asked for."""
+    import torch
+    _require_cuda(Cs, Ms, Zs, Y, L, info)
+    if strideC is None:
+        strideC = q * q
+    if batchSize is None:
+        batchSize = Cs.numel() // strideC
+    unknown = set(want) - set(_COLOUR_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_COLOUR_OUTPUTS}")
+    if Y is None and L is None and not want:
+        raise ValueError("no output requested")
+    wants_y = Y is not None or "Y" in want
+    if wants_y and Zs is None:
+        raise ValueError("Y needs the samples Zs")
+    nsample = Zs.numel() // (batchSize * q) if (wants_y and batchSize) else 0
+    if wants_y and batchSize and (nsample < 1 or Zs.numel() < batchSize * nsample * q):
+        raise ValueError("Zs needs batchSize*S*q elements, S >= 1")
+    if Y is None and wants_y:
+        Y = torch.empty(batchSize * nsample * q, dtype=Cs.dtype, device=Cs.device)
+    if L is None and "L" in want:
+        L = torch.empty(batchSize * q * q, dtype=Cs.dtype, device=Cs.device)
+    if any(t is not None and t.dtype != Cs.dtype for t in (Ms, Zs, Y, L)):
+        raise TypeError("Cs, Ms, Zs, Y and L must have one dtype")
+    if batchSize and Cs.numel() < (batchSize - 1) * strideC + q * q:
+        raise ValueError("Cs needs (batchSize-1)*strideC + q*q elements")
+    if (Ms is not None and Ms.numel() < batchSize * q) or (Y is not None and Y.numel() < batchSize * nsample * q) or \
+            (L is not None and L.numel() < batchSize * q * q):
+        raise ValueError("Ms needs batchSize*q elements, Y batchSize*S*q, L batchSize*q*q")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Cs.device):
+        _lib.check(_lib.lib().matinv_colour_batched(
+            _torch_dtype_code(Cs), q, nsample, p(Cs), strideC, p(Ms) if Y is not None else None, p(Zs) if Y is not None else None, p(Y), p(L),
+            batchSize, p(info), _stream_ptr(Cs)))
+    return Y, L
+
+
+def colour_batched_host(q, Cs: np.ndarray, Ms, Zs, want=_COLOUR_OUTPUTS):
+    """matinv_colour_batched_host on numpy batches (packed; Ms may be None, Zs may be None without "Y" in want): returns (Y, L, info), None
+    for the outputs not in want. Synchronous."""
+    Cs = np.ascontiguousarray(Cs)
+    Ms, Zs = (None if t is None else np.ascontiguousarray(t) for t in (Ms, Zs))
+    if any(t is not None and t.dtype != Cs.dtype for t in (Ms, Zs)):
+        raise TypeError("Cs, Ms and Zs must have one dtype")
+    unknown = set(want) - set(_COLOUR_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_COLOUR_OUTPUTS}")
+    batch = Cs.size // (q * q)
+    if "Y" in want and Zs is None:
+        raise ValueError("Y needs the samples Zs")
+    nsample = Zs.size // (batch * q) if ("Y" in want and batch) else 0
+    if "Y" in want and batch and nsample < 1:
+        raise ValueError("Zs needs batch*S*q elements, S >= 1")
+    if Ms is not None and Ms.size < batch * q:
+        raise ValueError("Ms smaller than batch*q")
+    Y = np.empty(batch * nsample * q, dtype=Cs.dtype) if "Y" in want else None
+    L = np.empty(batch * q * q, dtype=Cs.dtype) if "L" in want else None
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_colour_batched_host(
+        _np_dtype_code(Cs.dtype), q, nsample, p(Cs), q * q, p(Ms) if Y is not None else None, p(Zs) if Y is not None else None, p(Y), p(L),
+        batch, p(info)))
+    return Y, L, info
+
+
+def colour_kernel_name(dtype, q: int) -> str:
+    """matinv_colour_kernel_name: the kernel a colour request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_colour_kernel_name(code, q).decode()
+
+
+_SAMPLE_OUTPUTS = ("Y", "mean", "cov")
+
+
+def sample_batched(n, Bs, Cs, Ds, As, Es, Zs, Y=None, mean=None, cov=None, batchSize=None, info=None, want=("Y",)):
+    """Joint posterior samples of a GP at the Q query points of each covariance matrix on device tensors (matinv_sample_batched;
+    asynchronous on torch's current stream):  Y_k[:, s] = mean_k + chol(cov_k) z_ks  with mean and cov as predict_cov_batched returns
+    them for the same Bs, Cs, Ds, As, Es. Zs: batchSize*S*Q elements, sample s of matrix k a run of Q elements; Y has the same layout.
+    Y is always computed; mean (batchSize*Q) and cov (batchSize*Q*Q) are extra outputs, computed when their tensor is given or their name is
+    in `want`, and they do not change a bit of Y. Ds = None means the zero-mean posterior (and mean cannot be asked for). There is no
+    jitter parameter: Es is the caller's, and jitter goes on its diagonal. info: 0; 1 .. n when M is not positive definite (everything
+    NaN); n + j when column j of cov has the first non-positive pivot (Y NaN, mean and cov valid).
+    Returns (Y, mean, cov), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Ds, As, Es, Zs, Y, mean, cov, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    unknown = set(want) - set(_SAMPLE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_SAMPLE_OUTPUTS}")
+    if As is None or Zs is None:
+        raise ValueError("sampling needs the cross-covariance vectors As and the samples Zs")
+    nquery = As.numel() // (batchSize * n) if batchSize else 0
+    if batchSize and (nquery < 1 or As.numel() < batchSize * nquery * n):
+        raise ValueError("As needs batchSize*Q*n elements, Q >= 1")
+    nsample = Zs.numel() // (batchSize * nquery) if batchSize else 0
+    if batchSize and (nsample < 1 or Zs.numel() < batchSize * nsample * nquery):
+        raise ValueError("Zs needs batchSize*S*Q elements, S >= 1")
+    if Y is None:
+        Y = torch.empty(batchSize * nsample * nquery, dtype=Bs.dtype, device=Bs.device)
+    if mean is None and "mean" in want:
+        mean = torch.empty(batchSize * nquery, dtype=Bs.dtype, device=Bs.device)
+    if cov is None and "cov" in want:
+        cov = torch.empty(batchSize * nquery * nquery, dtype=Bs.dtype, device=Bs.device)
+    if mean is not None and Ds is None:
+        raise ValueError("mean needs the observations Ds")
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, As, Es, Zs, Y, mean, cov)):
+        raise TypeError("Bs, Cs, Ds, As, Es, Zs, Y, mean and cov must have one dtype")
+    if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds)) or (mean is not None and mean.numel() < batchSize * nquery) or \
+            any(t is not None and t.numel() < batchSize * nquery * nquery for t in (Es, cov)) or Y.numel() < batchSize * nsample * nquery:
+        raise ValueError("Cs and Ds need batchSize*n elements, mean batchSize*Q, Es and cov batchSize*Q*Q, Y batchSize*S*Q")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_sample_batched(
+            _torch_dtype_code(Bs), n, nquery, nsample, p(Bs), p(Cs), p(Ds), p(As), p(Es), p(Zs), p(Y), p(mean), p(cov), batchSize, p(info),
+            _stream_ptr(Bs)))
+    return Y, mean, cov
+
+
+def sample_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, Zs: np.ndarray, want=("Y",)):
+    """matinv_sample_batched_host on numpy batches (packed; Cs, Ds and Es may be None): returns (Y, mean, cov, info), None for the outputs
+    not in want. Synchronous."""
+    Bs, As, Zs = np.ascontiguousarray(Bs), np.ascontiguousarray(As), np.ascontiguousarray(Zs)
+    Cs, Ds, Es = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Ds, Es))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ds, As, Es, Zs)):
+        raise TypeError("Bs, Cs, Ds, As, Es and Zs must have one dtype")
+    unknown = set(want) - set(_SAMPLE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_SAMPLE_OUTPUTS}")
+    batch = Bs.size // (n * n)
+    nquery = As.size // (batch * n) if batch else 0
+    if batch and nquery < 1:
+        raise ValueError("As needs batch*Q*n elements, Q >= 1")
+    nsample = Zs.size // (batch * nquery) if batch else 0
+    if batch and nsample < 1:
+        raise ValueError("Zs needs batch*S*Q elements, S >= 1")
+    if "mean" in want and Ds is None:
+        raise ValueError("mean needs the observations Ds")
+    if any(t is not None and t.size < batch * n for t in (Cs, Ds)) or (Es is not None and Es.size < batch * nquery * nquery):
+        raise ValueError("Cs and Ds smaller than batch*n, or Es smaller than batch*Q*Q")
+    Y = np.empty(batch * nsample * nquery, dtype=Bs.dtype)
+    mean = np.empty(batch * nquery, dtype=Bs.dtype) if "mean" in want else None
+    cov = np.empty(batch * nquery * nquery, dtype=Bs.dtype) if "cov" in want else None
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_sample_batched_host(
+        _np_dtype_code(Bs.dtype), n, nquery, nsample, p(Bs), p(Cs), p(Ds), p(As), p(Es), p(Zs), p(Y), p(mean), p(cov), batch, p(info)))
+    return Y, mean, cov, info
+
+
 def logdet_kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> str:
     """matinv_logdet_kernel_name: the kernel a logdet request launches ("" when the request would be refused)."""
     code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)

@@ -1212,6 +1212,169 @@ int predict_cov_host(int n, int nquery, const void *hBs, const void *hCs, const 
     return MATINV_OK;
 }
 
+// ---- batched Cholesky factor and coloured samples Y = m + chol(C) Z (matinv_colour_batched) ---------------------------------------------
+int colour_check_args(int dtype, int q, int nsample, const void *dC, size_t strideC, const void *dZ, const void *dY, const void *dL,
+                      size_t batch)
+{
+    if (q < 1) return fail(MATINV_ERR_ARG, "q must be >= 1 (got %d)", q);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (!dC) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dY && !dL) return fail(MATINV_ERR_ARG, "no output requested (Y and L are both null)");
+    if (dY && !dZ) return fail(MATINV_ERR_ARG, "Y requested without the samples (dZ is null)");
+    if (dY && nsample < 1) return fail(MATINV_ERR_ARG, "nsample must be >= 1 with Y (got %d)", nsample);
+    if (strideC < (size_t)q * q) return fail(MATINV_ERR_ARG, "strideC %zu is smaller than q*q", strideC);
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (q > 1024) return fail(MATINV_ERR_UNSUPPORTED, "q=%d exceeds every kernel family built in (limit 1024)", q);
+    if (dY && nsample > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nsample=%d exceeds the limit of 1024 samples per call", nsample);
+    return MATINV_OK;
+}
+
+// q <= 96: the colour form of the one-wavefront SPD sweep. Beyond, to q = 1024: the colour form of the global-memory Cholesky kernel.
+// info_base: see launch_colour_tile (common.hpp).
+template <class T>
+int colour_dispatch(int q, int nsample, const void *dC, size_t strideC, const void *dM, const void *dZ, void *dY, void *dL, size_t batch,
+                    int *dInfo, int info_base, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *C = static_cast<const T *>(dC), *m = static_cast<const T *>(dM), *z = static_cast<const T *>(dZ);
+    T *Y = static_cast<T *>(dY), *L = static_cast<T *>(dL);
+    const hipError_t e = colour_tile_supports(q) ? launch_colour_tile<T>(q, nsample, C, strideC, m, z, Y, L, batch, dInfo, info_base, stream)
+                                                 : launch_colour_global<T>(q, nsample, C, strideC, m, z, Y, L, batch, dInfo, info_base, stream);
+    if (e != hipSuccess) return fail_hip(e, "colour launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int colour_host(int q, int nsample, const void *hC, size_t strideC, const void *hM, const void *hZ, void *hY, void *hL, size_t batch,
+                int *info)
+{
+    const size_t vec = (size_t)q * batch, mat = vec * q, ys = hY ? vec * (size_t)nsample : 0, cs = (batch - 1) * strideC + (size_t)q * q;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dC = nullptr, *dM = nullptr, *dZ = nullptr, *dY = nullptr, *dL = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dC), cs * sizeof(T));
+    if (e == hipSuccess && hM && hY) e = staging_alloc(reinterpret_cast<void **>(&dM), vec * sizeof(T));
+    if (e == hipSuccess && hY) e = staging_alloc(reinterpret_cast<void **>(&dZ), ys * sizeof(T));
+    if (e == hipSuccess && hY) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
+    if (e == hipSuccess && hL) e = staging_alloc(reinterpret_cast<void **>(&dL), mat * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dC, hC, cs * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dM) e = hipMemcpy(dM, hM, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dZ) e = hipMemcpy(dZ, hZ, ys * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = colour_dispatch<T>(q, nsample, dC, strideC, dM, dZ, dY, dL, batch, dInfo, 0, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hY) e = hipMemcpy(hY, dY, ys * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hL) e = hipMemcpy(hL, dL, mat * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dC), staging_free(dM), staging_free(dZ), staging_free(dY), staging_free(dL), staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "colour host<->device");
+    return MATINV_OK;
+}
+
+// ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
+int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
+                      const void *dY, const void *dMean, size_t batch)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 (got %d)", nquery);
+    if (nsample < 1) return fail(MATINV_ERR_ARG, "nsample must be >= 1 (got %d)", nsample);
+    if (!dBs || !dAs || !dZs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dY) return fail(MATINV_ERR_ARG, "no output requested (Y is null)");
+    if (dMean && !dDs) return fail(MATINV_ERR_ARG, "mean requested without the observations (dDs is null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    if (nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
+    if (nsample > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nsample=%d exceeds the limit of 1024 samples per call", nsample);
+    return MATINV_OK;
+}
+
+// Two launches per k-range chunk: the predictive-covariance route for this n (unchanged), then the colour route for Q on its cov and mean.
+// What the caller did not ask for goes into library scratch; the chunk is sized so that this scratch, together with the working copies the
+// global forms of either route allocate for the same chunk, fits the blocked-path workspace cap. dDs == nullptr: the zero-mean posterior
+// (no mean is computed, the colour route gets no m).
+template <class T>
+int sample_dispatch(int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs, const void *dEs,
+                    const void *dZs, void *dY, void *dMean, void *dCov, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const size_t Q = (size_t)nquery, qq = Q * Q, N = (size_t)n;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *d = static_cast<const T *>(dDs);
+    const T *a = static_cast<const T *>(dAs), *e_ = static_cast<const T *>(dEs), *z = static_cast<const T *>(dZs);
+    T *Y = static_cast<T *>(dY), *mean = static_cast<T *>(dMean), *cov = static_cast<T *>(dCov);
+    const bool own_mean = d && !mean, own_cov = !cov;
+    const size_t own = (own_mean ? Q : 0) + (own_cov ? qq : 0);
+    size_t chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = hipSuccess;
+    if (own) {
+        const size_t per = own + (predict_cov_tile_supports(n) ? 0 : N * (N + Q)) + (colour_tile_supports(nquery) ? 0 : qq);
+        chunk = blocked_workspace_cap() / (per * sizeof(T));
+        if (chunk < 1) chunk = 1;
+        if (chunk > batch) chunk = batch;
+        e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * own * sizeof(T), stream);
+        if (e != hipSuccess) return fail_hip(e, "sample workspace");
+    }
+    for (size_t off = 0; off < batch && rc == MATINV_OK; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        T *const cmean = !d ? nullptr : own_mean ? ws : mean + off * Q;
+        T *const ccov = own_cov ? ws + (own_mean ? chunk * Q : 0) : cov + off * qq;
+        int *const cinfo = dInfo ? dInfo + off : nullptr;
+        rc = predict_cov_dispatch<T>(n, nquery, B + off * N * N, c ? c + off * N : nullptr, d ? d + off * N : nullptr, a + off * Q * N,
+                                     e_ ? e_ + off * qq : nullptr, cmean, ccov, cnt, cinfo, stream);
+        if (rc == MATINV_OK)
+            rc = colour_dispatch<T>(nquery, nsample, ccov, qq, cmean, z + off * Q * nsample, Y + off * Q * nsample, nullptr, cnt, cinfo, n,
+                                    stream);
+    }
+    if (ws) {
+        const hipError_t e2 = scratch_free(ws, stream);
+        if (rc == MATINV_OK && e2 != hipSuccess) return fail_hip(e2, "sample workspace");
+    }
+    return rc;
+}
+
+template <class T>
+int sample_host(int n, int nquery, int nsample, const void *hBs, const void *hCs, const void *hDs, const void *hAs, const void *hEs,
+                const void *hZs, void *hY, void *hMean, void *hCov, size_t batch, int *info)
+{
+    const size_t vec = (size_t)n * batch, mat = vec * n, qs = batch * (size_t)nquery, qq = qs * (size_t)nquery, ys = qs * (size_t)nsample;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dA = nullptr, *dE = nullptr, *dZ = nullptr, *dY = nullptr, *dMean = nullptr, *dCov = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess && hDs) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dA), qs * (size_t)n * sizeof(T));
+    if (e == hipSuccess && hEs) e = staging_alloc(reinterpret_cast<void **>(&dE), qq * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dZ), ys * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
+    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMean), qs * sizeof(T));
+    if (e == hipSuccess && hCov) e = staging_alloc(reinterpret_cast<void **>(&dCov), qq * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hDs) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dA, hAs, qs * (size_t)n * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dE) e = hipMemcpy(dE, hEs, qq * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dZ, hZs, ys * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = sample_dispatch<T>(n, nquery, nsample, dB, dC, dD, dA, dE, dZ, dY, dMean, dCov, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hY, dY, ys * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMean, qs * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hCov) e = hipMemcpy(hCov, dCov, qq * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dA), staging_free(dE), staging_free(dZ), staging_free(dY);
+    staging_free(dMean), staging_free(dCov), staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "sample host<->device");
+    return MATINV_OK;
+}
+
 template <class T>
 int lu_kernel(int n)
 {
@@ -1612,6 +1775,51 @@ int matinv_predict_cov_batched_host(int dtype, int n, int nquery, const void *hB
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return predict_cov_host<double>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
     return predict_cov_host<float>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
+}
+
+int matinv_colour_batched(int dtype, int q, int nsample, const void *dC, size_t strideC, const void *dM, const void *dZ, void *dY, void *dL,
+                          size_t batch, int *dInfo, void *stream)
+{
+    int rc = colour_check_args(dtype, q, nsample, dC, strideC, dZ, dY, dL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return colour_dispatch<double>(q, nsample, dC, strideC, dM, dZ, dY, dL, batch, dInfo, 0, st);
+    return colour_dispatch<float>(q, nsample, dC, strideC, dM, dZ, dY, dL, batch, dInfo, 0, st);
+}
+
+const char *matinv_colour_kernel_name(int dtype, int q)
+{
+    if (q < 1 || q > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return colour_tile_supports(q) ? name_colour_tile(dtype == MATINV_F64, q) : name_colour_global(dtype == MATINV_F64);
+}
+
+int matinv_colour_batched_host(int dtype, int q, int nsample, const void *hC, size_t strideC, const void *hM, const void *hZ, void *hY,
+                               void *hL, size_t batch, int *info)
+{
+    int rc = colour_check_args(dtype, q, nsample, hC, strideC, hZ, hY, hL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return colour_host<double>(q, nsample, hC, strideC, hM, hZ, hY, hL, batch, info);
+    return colour_host<float>(q, nsample, hC, strideC, hM, hZ, hY, hL, batch, info);
+}
+
+int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs,
+                          const void *dEs, const void *dZs, void *dY, void *dMean, void *dCov, size_t batch, int *dInfo, void *stream)
+{
+    int rc = sample_check_args(dtype, n, nquery, nsample, dBs, dDs, dAs, dZs, dY, dMean, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64)
+        return sample_dispatch<double>(n, nquery, nsample, dBs, dCs, dDs, dAs, dEs, dZs, dY, dMean, dCov, batch, dInfo, st);
+    return sample_dispatch<float>(n, nquery, nsample, dBs, dCs, dDs, dAs, dEs, dZs, dY, dMean, dCov, batch, dInfo, st);
+}
+
+int matinv_sample_batched_host(int dtype, int n, int nquery, int nsample, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
+                               const void *hEs, const void *hZs, void *hY, void *hMean, void *hCov, size_t batch, int *info)
+{
+    int rc = sample_check_args(dtype, n, nquery, nsample, hBs, hDs, hAs, hZs, hY, hMean, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return sample_host<double>(n, nquery, nsample, hBs, hCs, hDs, hAs, hEs, hZs, hY, hMean, hCov, batch, info);
+    return sample_host<float>(n, nquery, nsample, hBs, hCs, hDs, hAs, hEs, hZs, hY, hMean, hCov, batch, info);
 }
 
 int matinv_loo_grad_batched(int dtype, int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad,

@@ -416,6 +416,22 @@ hipError_t launch_loo_grad_global(int n, int nparam, const T *Bs, const T *Cs, c
                                   size_t batch, int *info, hipStream_t stream);
 const char *name_loo_grad_global(bool f64);
 
+// Batched Cholesky factor and coloured samples Y = m + chol(C) Z (matinv_colour_batched): Cs: matrix k at k * stride, n x n column-major,
+// lower triangle read; Ms (optional): batch * n; Zs: batch * n * nsample, sample s of matrix k a run of n elements; Ys: as Zs; Ls:
+// batch * n^2, column-major, strict upper triangle written as zeros. Ys and Ls are each optional; Zs is read with Ys only.
+// info_base != 0 (matinv_sample_batched): info holds the codes of an earlier stage; a non-zero one stands, a failure here is info_base + column.
+// (a) the colour form of the one-wavefront SPD sweep, n <= 96 (colour_tile_kernels.hip, colour_tile_f32_kernels.hip)
+bool colour_tile_supports(int n);
+template <class T>
+hipError_t launch_colour_tile(int n, int nsample, const T *Cs, size_t stride, const T *Ms, const T *Zs, T *Ys, T *Ls, size_t batch, int *info,
+                              int info_base, hipStream_t stream);
+const char *name_colour_tile(bool f64, int n);
+// (b) the colour form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_colour_global(int n, int nsample, const T *Cs, size_t stride, const T *Ms, const T *Zs, T *Ys, T *Ls, size_t batch,
+                                int *info, int info_base, hipStream_t stream);
+const char *name_colour_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

@@ -957,4 +957,93 @@ const char *name_loo_grad_global(bool f64)
     return f64 ? "matinv_chol_global<double, true, true, true, true, true>" : "matinv_chol_global<float, true, true, true, true, true>";
 }
 
+// ---- Cholesky factor and coloured samples, 96 < n <= 1024 (matinv_colour_batched behind colour_tile_impl.hpp) ---------------------------
+// The colour form of matinv_chol_global: one more template argument again ("Posterior samples"). The lower triangle of C is
+// factored in the matrix's slice of library scratch, as above. Then
+//     L out, the strict upper triangle as zeros;   per (row i, sample s), one thread each:  Y[i][s] = m_i + sum_k L[i][k] z_s[k], k ascending
+// so the order of operations of an element knows nothing of S or of the sample's position. Not SPD: info = the failing column + 1 and
+// every requested output NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Cs, size_t stride, const T *Ms, const T *Zs, int nsample, T *Ys,
+                                                                 T *Ls, int *info, int info_base, int n, T *workspace, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR, "the seven-argument form is the colour kernel");
+    __shared__ T col[1024];
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Cs + k_mat * stride;
+    const size_t nn = (size_t)n * n, ns = (size_t)n * nsample;
+    T *W = workspace + (size_t)blockIdx.x * nn;
+    T *Lm = Ls ? Ls + k_mat * nn : nullptr, *Ym = Ys ? Ys + k_mat * ns : nullptr;
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r >= c) W[e] = A[e];
+    }
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        if (Lm)
+            for (size_t e = t; e < nn; e += GL_THREADS) Lm[e] = nan_of<T>();
+        if (Ym)
+            for (size_t e = t; e < ns; e += GL_THREADS) Ym[e] = nan_of<T>();
+        if (info && t == 0) {  // the code of an earlier stage stands (colour_tile_body)
+            const int prior = info_base ? info[k_mat] : 0;
+            info[k_mat] = prior ? prior : info_base + bad;
+        }
+        return;
+    }
+    if (Lm)
+        for (size_t e = t; e < nn; e += GL_THREADS) {
+            const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+            Lm[e] = r >= c ? W[e] : (T)0;
+        }
+    if (Ym) {
+        const T *Z = Zs + k_mat * ns;
+        for (size_t e = t; e < ns; e += GL_THREADS) {
+            const int s = (int)(e / n), i = (int)(e - (size_t)s * n);
+            const T *z = Z + (size_t)s * n;
+            T a = 0;
+            for (int k = 0; k <= i; ++k) a += W[(size_t)k * n + i] * z[k];
+            Ym[e] = (Ms ? Ms[k_mat * n + i] : (T)0) + a;
+        }
+    }
+    if (info && t == 0 && !info_base) info[k_mat] = 0;  // after an earlier stage a factored matrix has its 0 already
+}
+
+template <class T>
+hipError_t launch_colour_global(int n, int nsample, const T *Cs, size_t stride, const T *Ms, const T *Zs, T *Ys, T *Ls, size_t batch,
+                                int *info, int info_base, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_loo_global)
+    const size_t per = (size_t)n * n;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Cs,
+                           stride, Ms, Zs, nsample, Ys, Ls, info, info_base, n, ws, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_colour_global<double>(int, int, const double *, size_t, const double *, const double *, double *, double *, size_t,
+                                                 int *, int, hipStream_t);
+template hipError_t launch_colour_global<float>(int, int, const float *, size_t, const float *, const float *, float *, float *, size_t,
+                                                int *, int, hipStream_t);
+
+const char *name_colour_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true>";
+}
+
 }  // namespace matinv

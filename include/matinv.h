@@ -294,6 +294,47 @@ const char *matinv_predict_cov_kernel_name(int dtype, int n);
 int matinv_predict_cov_batched_host(int dtype, int n, int nquery, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
                                     const void *hEs, void *hMean, void *hCov, size_t batch, int *info);
 
+/* The lower Cholesky factor of batched SPD matrices and samples coloured by it, device-resident:
+ *   C_k = L_k L_k^T,   Y_k[:, s] = m_k + L_k z_ks      for the nsample vectors z_ks of matrix k
+ * dC: matrix k is q x q, column-major, at element k*strideC (strideC >= q*q); only its lower triangle is read. dM: batch*q elements, or
+ * NULL (m = 0). dZ: batch*q*nsample elements, sample s of matrix k the run of q elements at (k*nsample + s)*q. dY: the same layout.
+ * dL: batch*q*q elements, column-major per matrix: the lower triangle with a positive diagonal, the strict upper triangle written as
+ * exact zeros. dY and dL are each optional (both NULL: MATINV_ERR_ARG), and which of them is requested does not change a bit of the
+ * other; dZ and nsample >= 1 are needed with dY only. 1 <= q <= 1024 and nsample <= 1024 (beyond: MATINV_ERR_UNSUPPORTED). No input is
+ * modified (outputs must not overlap inputs). Bit for bit, L_k depends on C_k alone and Y_k[:, s] on C_k, m_k and z_ks alone -- not on
+ * batch, nsample or the position of the sample; Z = 0 returns the bits of m (one exception: an element m_i = -0.0 comes back as +0.0,
+ * because the zero products are added to it). The library draws no random numbers: Z is the caller's,
+ * which keeps every result reproducible. dInfo (optional): 0, or the 1-based column of the first non-positive (or NaN) pivot -- every
+ * requested output of that matrix is then NaN; there is no jitter and no pivoting (a semi-definite C is the caller's to regularise).
+ * q <= 96: the colour form of the one-wavefront SPD tile sweep, the samples in groups of 16 on the MFMA unit (q^2/2 + q + q nsample
+ * elements read, q^2 + q nsample written). Beyond, to q = 1024: the colour form of the global-memory Cholesky kernel on a working copy
+ * in library scratch. Asynchronous, no host synchronisation. */
+int matinv_colour_batched(int dtype, int q, int nsample, const void *dC, size_t strideC, const void *dM, const void *dZ, void *dY, void *dL,
+                          size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a colour request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_colour_kernel_name(int dtype, int q);
+/* Host-pointer form (hM, `info` and each output optional; hZ is read only with hY). Synchronous. */
+int matinv_colour_batched_host(int dtype, int q, int nsample, const void *hC, size_t strideC, const void *hM, const void *hZ, void *hY,
+                               void *hL, size_t batch, int *info);
+
+/* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
+ * for the same dBs, dCs, dDs, dAs, dEs,
+ *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
+ * It is two launches: the predictive-covariance route for this n, then the colour route for nquery (their kernels are named by
+ * matinv_predict_cov_kernel_name(dtype, n) and matinv_colour_kernel_name(dtype, nquery)). dMean (batch*nquery) and dCov
+ * (batch*nquery^2) are optional extra outputs and carry the bits of matinv_predict_cov_batched; Y carries the bits of
+ * matinv_colour_batched on that cov and mean, whether or not they are requested (what is not requested lives in library scratch, in
+ * k-range chunks under MATINV_BLOCKED_WS_MB). dDs == NULL means the zero-mean posterior: Y = chol(cov) z, and dMean must then be NULL
+ * too. n, nquery, nsample <= 1024 (beyond: MATINV_ERR_UNSUPPORTED). dInfo (optional): 0; the 1-based column (1 .. n) of the first
+ * non-positive pivot of M -- every output of that matrix is then NaN; or n + j when column j of cov has the first non-positive pivot --
+ * Y is then NaN while mean and cov stay valid. There is no jitter parameter: E is the caller's, and jitter goes on its diagonal.
+ * Asynchronous, no host synchronisation. */
+int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs,
+                          const void *dEs, const void *dZs, void *dY, void *dMean, void *dCov, size_t batch, int *dInfo, void *stream);
+/* Host-pointer form (packed; hCs, hDs, hEs, hMean, hCov and `info` optional). Synchronous. */
+int matinv_sample_batched_host(int dtype, int n, int nquery, int nsample, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
+                               const void *hEs, const void *hZs, void *hY, void *hMean, void *hCov, size_t batch, int *info);
+
 /* Gradients of the GP leave-one-out log pseudo-likelihood (the logpl matinv_loo_batched returns; Rasmussen & Williams 5.4.2),
  * device-resident. With M_k = B_k + diag(c_k), K = M^-1, alpha = K d, kappa_i = K_ii and nparam symmetric derivative matrices
  * dM_p = dM / d theta_p per matrix:
