@@ -841,6 +841,96 @@ def colour_kernel_name(dtype, q: int) -> str:
     return _lib.lib().matinv_colour_kernel_name(code, q).decode()
 
 
+_WHITEN_OUTPUTS = ("W", "maha", "logdet", "logpdf")
+
+
+def whiten_batched(q, Cs, Ms, Xs, W=None, maha=None, logdet=None, logpdf=None, batchSize=None, info=None, want=_WHITEN_OUTPUTS,
+                   strideC=None):
+    """Whitened points, squared Mahalanobis distances, log-determinants and Gaussian log-densities of batched SPD matrices on device tensors
+    (matinv_whiten_batched; asynchronous on torch's current stream) -- the inverse map of colour_batched. With C_k = L_k L_k^T:
+        W_k[:, s] = L_k^-1 (x_ks - m_k),  maha_k[s] = ||W_k[:, s]||^2,  logdet_k = log det C_k,
+        logpdf_k[s] = -(maha_k[s] + logdet_k + q log 2 pi) / 2
+    Cs: matrix k is q x q, column-major, at element k*strideC (default q*q), only the lower triangle read. Ms: batchSize*q elements or None
+    (m = 0). Xs: batchSize*S*q elements, point s of matrix k a run of q elements; S is Xs.numel() // (batchSize*q). W has the layout of
+    Xs; maha and logpdf are batchSize*S, logdet is batchSize.
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one; which are asked for
+    changes no bit of the others. Xs may be None when only logdet is asked for. No input is modified. Not positive definite: info = the
+    1-based column of the first non-positive pivot and every requested output of that matrix NaN; there is no jitter.
+    Returns (W, maha, logdet, logpdf), None for what was not asked for."""
+    import torch
+    _require_cuda(Cs, Ms, Xs, W, maha, logdet, logpdf, info)
+    if strideC is None:
+        strideC = q * q
+    if batchSize is None:
+        batchSize = Cs.numel() // strideC
+    unknown = set(want) - set(_WHITEN_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_WHITEN_OUTPUTS}")
+    given = dict(W=W, maha=maha, logdet=logdet, logpdf=logpdf)
+    asked = {k: given[k] is not None or k in want for k in _WHITEN_OUTPUTS}
+    if not any(asked.values()):
+        raise ValueError("no output requested")
+    points = asked["W"] or asked["maha"] or asked["logpdf"]
+    if points and Xs is None:
+        raise ValueError("W, maha and logpdf need the points Xs")
+    npoint = Xs.numel() // (batchSize * q) if (points and batchSize) else 0
+    if points and batchSize and (npoint < 1 or Xs.numel() < batchSize * npoint * q):
+        raise ValueError("Xs needs batchSize*S*q elements, S >= 1")
+    sizes = dict(W=batchSize * npoint * q, maha=batchSize * npoint, logdet=batchSize, logpdf=batchSize * npoint)
+    for k in _WHITEN_OUTPUTS:
+        if asked[k] and given[k] is None:
+            given[k] = torch.empty(sizes[k], dtype=Cs.dtype, device=Cs.device)
+    if any(t is not None and t.dtype != Cs.dtype for t in (Ms, Xs, *given.values())):
+        raise TypeError("Cs, Ms, Xs, W, maha, logdet and logpdf must have one dtype")
+    if batchSize and Cs.numel() < (batchSize - 1) * strideC + q * q:
+        raise ValueError("Cs needs (batchSize-1)*strideC + q*q elements")
+    if (Ms is not None and Ms.numel() < batchSize * q) or any(given[k] is not None and given[k].numel() < sizes[k] for k in _WHITEN_OUTPUTS):
+        raise ValueError("Ms needs batchSize*q elements, W batchSize*S*q, maha and logpdf batchSize*S, logdet batchSize")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Cs.device):
+        _lib.check(_lib.lib().matinv_whiten_batched(
+            _torch_dtype_code(Cs), q, npoint, p(Cs), strideC, p(Ms) if points else None, p(Xs) if points else None, p(given["W"]),
+            p(given["maha"]), p(given["logdet"]), p(given["logpdf"]), batchSize, p(info), _stream_ptr(Cs)))
+    return given["W"], given["maha"], given["logdet"], given["logpdf"]
+
+
+def whiten_batched_host(q, Cs: np.ndarray, Ms, Xs, want=_WHITEN_OUTPUTS):
+    """matinv_whiten_batched_host on numpy batches (packed; Ms may be None, Xs may be None when only "logdet" is in want): returns
+    (W, maha, logdet, logpdf, info), None for the outputs not in want. Synchronous."""
+    Cs = np.ascontiguousarray(Cs)
+    Ms, Xs = (None if t is None else np.ascontiguousarray(t) for t in (Ms, Xs))
+    if any(t is not None and t.dtype != Cs.dtype for t in (Ms, Xs)):
+        raise TypeError("Cs, Ms and Xs must have one dtype")
+    unknown = set(want) - set(_WHITEN_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_WHITEN_OUTPUTS}")
+    batch = Cs.size // (q * q)
+    points = bool(set(want) & {"W", "maha", "logpdf"})
+    if points and Xs is None:
+        raise ValueError("W, maha and logpdf need the points Xs")
+    npoint = Xs.size // (batch * q) if (points and batch) else 0
+    if points and batch and npoint < 1:
+        raise ValueError("Xs needs batch*S*q elements, S >= 1")
+    if Ms is not None and Ms.size < batch * q:
+        raise ValueError("Ms smaller than batch*q")
+    sizes = dict(W=batch * npoint * q, maha=batch * npoint, logdet=batch, logpdf=batch * npoint)
+    out = {k: np.empty(sizes[k], dtype=Cs.dtype) if k in want else None for k in _WHITEN_OUTPUTS}
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_whiten_batched_host(
+        _np_dtype_code(Cs.dtype), q, npoint, p(Cs), q * q, p(Ms) if points else None, p(Xs) if points else None, p(out["W"]), p(out["maha"]),
+        p(out["logdet"]), p(out["logpdf"]), batch, p(info)))
+    return out["W"], out["maha"], out["logdet"], out["logpdf"], info
+
+
+def whiten_kernel_name(dtype, q: int) -> str:
+    """matinv_whiten_kernel_name: the kernel a whiten request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_whiten_kernel_name(code, q).decode()
+
+
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")
 
 

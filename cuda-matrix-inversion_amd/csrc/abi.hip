@@ -1274,6 +1274,76 @@ int colour_host(int q, int nsample, const void *hC, size_t strideC, const void *
     return MATINV_OK;
 }
 
+// ---- batched whitening W = chol(C)^-1 (X - m), Mahalanobis distances and Gaussian log-density (matinv_whiten_batched) ------------------
+// the checks of colour_check_args, in its order
+int whiten_check_args(int dtype, int q, int npoint, const void *dC, size_t strideC, const void *dX, const void *dW, const void *dMaha,
+                      const void *dLogdet, const void *dLogpdf, size_t batch)
+{
+    const bool points = dW || dMaha || dLogpdf;
+    if (q < 1) return fail(MATINV_ERR_ARG, "q must be >= 1 (got %d)", q);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (!dC) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!points && !dLogdet) return fail(MATINV_ERR_ARG, "no output requested (W, maha, logdet and logpdf are all null)");
+    if (points && !dX) return fail(MATINV_ERR_ARG, "W, maha or logpdf requested without the points (dX is null)");
+    if (points && npoint < 1) return fail(MATINV_ERR_ARG, "npoint must be >= 1 with W, maha or logpdf (got %d)", npoint);
+    if (strideC < (size_t)q * q) return fail(MATINV_ERR_ARG, "strideC %zu is smaller than q*q", strideC);
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (q > 1024) return fail(MATINV_ERR_UNSUPPORTED, "q=%d exceeds every kernel family built in (limit 1024)", q);
+    if (points && npoint > 1024) return fail(MATINV_ERR_UNSUPPORTED, "npoint=%d exceeds the limit of 1024 points per call", npoint);
+    return MATINV_OK;
+}
+
+// q <= 96: the whiten form of the one-wavefront SPD sweep. Beyond, to q = 1024: the whiten form of the global-memory Cholesky kernel.
+template <class T>
+int whiten_dispatch(int q, int npoint, const void *dC, size_t strideC, const void *dM, const void *dX, void *dW, void *dMaha, void *dLogdet,
+                    void *dLogpdf, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *C = static_cast<const T *>(dC), *m = static_cast<const T *>(dM), *x = static_cast<const T *>(dX);
+    T *W = static_cast<T *>(dW), *mh = static_cast<T *>(dMaha), *ld = static_cast<T *>(dLogdet), *lp = static_cast<T *>(dLogpdf);
+    const hipError_t e = whiten_tile_supports(q) ? launch_whiten_tile<T>(q, npoint, C, strideC, m, x, W, mh, ld, lp, batch, dInfo, stream)
+                                                 : launch_whiten_global<T>(q, npoint, C, strideC, m, x, W, mh, ld, lp, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "whiten launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int whiten_host(int q, int npoint, const void *hC, size_t strideC, const void *hM, const void *hX, void *hW, void *hMaha, void *hLogdet,
+                void *hLogpdf, size_t batch, int *info)
+{
+    const bool points = hW || hMaha || hLogpdf;
+    const size_t vec = (size_t)q * batch, ps = points ? batch * (size_t)npoint : 0, xs = vec * (points ? (size_t)npoint : 0);
+    const size_t cs = (batch - 1) * strideC + (size_t)q * q;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dC = nullptr, *dM = nullptr, *dX = nullptr, *dW = nullptr, *dMh = nullptr, *dLd = nullptr, *dLp = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dC), cs * sizeof(T));
+    if (e == hipSuccess && hM && points) e = staging_alloc(reinterpret_cast<void **>(&dM), vec * sizeof(T));
+    if (e == hipSuccess && points) e = staging_alloc(reinterpret_cast<void **>(&dX), xs * sizeof(T));
+    if (e == hipSuccess && hW) e = staging_alloc(reinterpret_cast<void **>(&dW), xs * sizeof(T));
+    if (e == hipSuccess && hMaha) e = staging_alloc(reinterpret_cast<void **>(&dMh), ps * sizeof(T));
+    if (e == hipSuccess && hLogdet) e = staging_alloc(reinterpret_cast<void **>(&dLd), batch * sizeof(T));
+    if (e == hipSuccess && hLogpdf) e = staging_alloc(reinterpret_cast<void **>(&dLp), ps * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dC, hC, cs * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dM) e = hipMemcpy(dM, hM, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dX) e = hipMemcpy(dX, hX, xs * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = whiten_dispatch<T>(q, npoint, dC, strideC, dM, dX, dW, dMh, dLd, dLp, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hW) e = hipMemcpy(hW, dW, xs * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hMaha) e = hipMemcpy(hMaha, dMh, ps * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hLogdet) e = hipMemcpy(hLogdet, dLd, batch * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hLogpdf) e = hipMemcpy(hLogpdf, dLp, ps * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dC), staging_free(dM), staging_free(dX), staging_free(dW), staging_free(dMh), staging_free(dLd), staging_free(dLp);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "whiten host<->device");
+    return MATINV_OK;
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -1800,6 +1870,31 @@ int matinv_colour_batched_host(int dtype, int q, int nsample, const void *hC, si
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return colour_host<double>(q, nsample, hC, strideC, hM, hZ, hY, hL, batch, info);
     return colour_host<float>(q, nsample, hC, strideC, hM, hZ, hY, hL, batch, info);
+}
+
+int matinv_whiten_batched(int dtype, int q, int npoint, const void *dC, size_t strideC, const void *dM, const void *dX, void *dW, void *dMaha,
+                          void *dLogdet, void *dLogpdf, size_t batch, int *dInfo, void *stream)
+{
+    int rc = whiten_check_args(dtype, q, npoint, dC, strideC, dX, dW, dMaha, dLogdet, dLogpdf, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64) return whiten_dispatch<double>(q, npoint, dC, strideC, dM, dX, dW, dMaha, dLogdet, dLogpdf, batch, dInfo, st);
+    return whiten_dispatch<float>(q, npoint, dC, strideC, dM, dX, dW, dMaha, dLogdet, dLogpdf, batch, dInfo, st);
+}
+
+const char *matinv_whiten_kernel_name(int dtype, int q)
+{
+    if (q < 1 || q > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return whiten_tile_supports(q) ? name_whiten_tile(dtype == MATINV_F64, q) : name_whiten_global(dtype == MATINV_F64);
+}
+
+int matinv_whiten_batched_host(int dtype, int q, int npoint, const void *hC, size_t strideC, const void *hM, const void *hX, void *hW,
+                               void *hMaha, void *hLogdet, void *hLogpdf, size_t batch, int *info)
+{
+    int rc = whiten_check_args(dtype, q, npoint, hC, strideC, hX, hW, hMaha, hLogdet, hLogpdf, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64) return whiten_host<double>(q, npoint, hC, strideC, hM, hX, hW, hMaha, hLogdet, hLogpdf, batch, info);
+    return whiten_host<float>(q, npoint, hC, strideC, hM, hX, hW, hMaha, hLogdet, hLogpdf, batch, info);
 }
 
 int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs,

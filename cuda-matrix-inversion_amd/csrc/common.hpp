@@ -432,6 +432,21 @@ hipError_t launch_colour_global(int n, int nsample, const T *Cs, size_t stride, 
                                 int *info, int info_base, hipStream_t stream);
 const char *name_colour_global(bool f64);
 
+// Batched whitening, Mahalanobis distances and Gaussian log-density (matinv_whiten_batched): Cs, Ms as above; Xs: batch * n * npoint, point
+// s of matrix k a run of n elements; Ws: as Xs, L^-1 (x - m); Mh: batch * npoint, ||w||^2; Ld: batch, log det C; Lp: batch * npoint,
+// -1/2 (maha + logdet + n log 2 pi). Every output is optional; Xs is read only with Ws, Mh or Lp.
+// (a) the whiten form of the one-wavefront SPD sweep, n <= 96 (whiten_tile_kernels.hip, whiten_tile_f32_kernels.hip)
+bool whiten_tile_supports(int n);
+template <class T>
+hipError_t launch_whiten_tile(int n, int npoint, const T *Cs, size_t stride, const T *Ms, const T *Xs, T *Ws, T *Mh, T *Ld, T *Lp,
+                              size_t batch, int *info, hipStream_t stream);
+const char *name_whiten_tile(bool f64, int n);
+// (b) the whiten form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_whiten_global(int n, int npoint, const T *Cs, size_t stride, const T *Ms, const T *Xs, T *Ws, T *Mh, T *Ld, T *Lp,
+                                size_t batch, int *info, hipStream_t stream);
+const char *name_whiten_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

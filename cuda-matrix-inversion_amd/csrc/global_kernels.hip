@@ -8,6 +8,7 @@
 // It is a functional path (2 n^3 * sizeof(T) bytes of cache traffic per matrix), not a tuned one: the blocked, MFMA-based
 // large-n path is listed as next in DESIGN.md.
 #include "common.hpp"
+#include "pivot_product.hpp"
 
 namespace matinv {
 
@@ -1044,6 +1045,112 @@ const char *name_colour_global(bool f64)
 {
     return f64 ? "matinv_chol_global<double, true, true, true, true, true, true>"
                : "matinv_chol_global<float, true, true, true, true, true, true>";
+}
+
+// ---- whitening, Mahalanobis distances and Gaussian log-density, 96 < n <= 1024 (matinv_whiten_batched behind whiten_tile_impl.hpp) ------
+// The whiten form of matinv_chol_global: one more template argument again ("Whitening"). The lower triangle of C is factored in
+// the matrix's slice of library scratch, as above. Thread 0 folds the diagonal of L into a PivotProduct: logdet = 2 log prod L_ii. Then one
+// thread per point, on the point's own n elements of scratch behind the factor: v = x - m; columns k ascending: w_k = v_k / L_kk,
+// maha += w_k^2, v_i -= L_ik w_k for i > k. The order of operations of a point knows nothing of S or of the point's position. Not SPD:
+// info = the failing column + 1 and every requested output NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves
+// matrix first + blockIdx.x; `per` elements of workspace each (n^2, and n npoint more when the points are read).
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR, bool WHITEN>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Cs, size_t stride, const T *Ms, const T *Xs, int npoint, T *Ws,
+                                                                 T *Mh, T *Ld, T *Lp, int *info, int n, T *workspace, size_t per,
+                                                                 size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR && WHITEN, "the eight-argument form is the whiten kernel");
+    __shared__ T col[1024];
+    __shared__ T s_ld;
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Cs + k_mat * stride;
+    const bool points = Ws || Mh || Lp;  // block-uniform
+    const size_t nn = (size_t)n * n, np = points ? (size_t)npoint : 0, ns = (size_t)n * np;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *V = W + nn;
+    T *Wm = Ws ? Ws + k_mat * ns : nullptr;
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r >= c) W[e] = A[e];
+    }
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        if (Wm)
+            for (size_t e = t; e < ns; e += GL_THREADS) Wm[e] = nan_of<T>();
+        for (size_t s = t; s < np; s += GL_THREADS) {
+            if (Mh) Mh[k_mat * np + s] = nan_of<T>();
+            if (Lp) Lp[k_mat * np + s] = nan_of<T>();
+        }
+        if (Ld && t == 0) Ld[k_mat] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    if (t == 0) {
+        PivotProduct<T> prod;
+        for (int i = 0; i < n; ++i) prod.fold(W[(size_t)i * n + i]);
+        const T ld = (T)2 * prod.log_value();
+        s_ld = ld;
+        if (Ld) Ld[k_mat] = ld;
+    }
+    __syncthreads();
+    const T ld = s_ld;
+    for (size_t s = t; s < np; s += GL_THREADS) {
+        const T *x = Xs + k_mat * ns + s * n;
+        T *v = V + s * n;
+        for (int i = 0; i < n; ++i) v[i] = x[i] - (Ms ? Ms[k_mat * n + i] : (T)0);
+        T mh = 0;
+        for (int k = 0; k < n; ++k) {
+            const T *lk = W + (size_t)k * n;
+            const T w = v[k] / lk[k];
+            v[k] = w;
+            mh += w * w;
+            for (int i = k + 1; i < n; ++i) v[i] -= lk[i] * w;
+        }
+        if (Wm)
+            for (int i = 0; i < n; ++i) Wm[s * n + i] = v[i];
+        if (Mh) Mh[k_mat * np + s] = mh;
+        // log 2 pi
+        if (Lp) Lp[k_mat * np + s] = (T)-0.5 * ((mh + ld) + (T)n * (T)1.83787706640934548356);
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_whiten_global(int n, int npoint, const T *Cs, size_t stride, const T *Ms, const T *Xs, T *Ws, T *Mh, T *Ld, T *Lp,
+                                size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_loo_global)
+    const size_t per = (size_t)n * n + ((Ws || Mh || Lp) ? (size_t)n * npoint : 0);
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream,
+                           Cs, stride, Ms, Xs, npoint, Ws, Mh, Ld, Lp, info, n, ws, per, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_whiten_global<double>(int, int, const double *, size_t, const double *, const double *, double *, double *,
+                                                 double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_whiten_global<float>(int, int, const float *, size_t, const float *, const float *, float *, float *, float *,
+                                                float *, size_t, int *, hipStream_t);
+
+const char *name_whiten_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true, true>";
 }
 
 }  // namespace matinv

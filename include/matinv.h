@@ -317,6 +317,34 @@ const char *matinv_colour_kernel_name(int dtype, int q);
 int matinv_colour_batched_host(int dtype, int q, int nsample, const void *hC, size_t strideC, const void *hM, const void *hZ, void *hY,
                                void *hL, size_t batch, int *info);
 
+/* Whitened points, squared Mahalanobis distances, the log-determinant and the Gaussian log-density of batched SPD matrices,
+ * device-resident -- the inverse map of matinv_colour_batched. With C_k = L_k L_k^T and the npoint points x_ks of matrix k:
+ *   W_k[:, s]    = L_k^-1 (x_ks - m_k)
+ *   maha_k[s]    = ||W_k[:, s]||^2                 = (x - m)^T C^-1 (x - m)
+ *   logdet_k     = log det C_k = 2 sum_i log L_ii
+ *   logpdf_k[s]  = -1/2 (maha_k[s] + logdet_k + q log 2 pi)        the log-density of N(m_k, C_k) at x_ks
+ * dC, strideC, dM: as in matinv_colour_batched (lower triangle read; dM NULL: m = 0). dX: batch*q*npoint elements, point s of matrix k
+ * the run of q elements at (k*npoint + s)*q. dW: the same layout. dMaha, dLogpdf: batch*npoint elements, at k*npoint + s. dLogdet: batch
+ * elements. Every output is optional and at least one is required (all NULL: MATINV_ERR_ARG); which of them are requested does not
+ * change a bit of the others. dX and npoint >= 1 are needed with dW, dMaha or dLogpdf only: with dLogdet alone dX is not read and may be
+ * NULL. 1 <= q <= 1024 and npoint <= 1024 (beyond: MATINV_ERR_UNSUPPORTED); the argument checks are those of matinv_colour_batched, in
+ * its order. No input is modified (outputs must not overlap inputs). Bit for bit, logdet_k depends on C_k alone and W, maha and logpdf of
+ * a point on C_k, m_k and that point alone -- not on batch, npoint or the position of the point. x = m returns W = +0.0 in every element
+ * (also where x and m are -0.0) and maha = +0.0. logdet is taken from the running product of the pivots as mantissa and exponent, one
+ * logarithm per matrix: it neither overflows nor underflows where det C would. dInfo (optional): 0, or the 1-based column of the first
+ * non-positive (or NaN) pivot -- every requested output of that matrix is then NaN; there is no jitter, no pivoting and no fallback launch.
+ * q <= 96: the whiten form of the one-wavefront SPD tile sweep; the factor stays in registers in the lane layout of the MFMA's A
+ * operand and the points are solved in groups of 16, two dependent MFMAs per block of four columns (q^2/2 + q + q npoint elements read,
+ * q npoint + 2 npoint + 1 written). Beyond, to q = 1024: the whiten form of the global-memory Cholesky kernel on a working copy in
+ * library scratch (k-range chunks under MATINV_BLOCKED_WS_MB), one thread per point. Asynchronous, no host synchronisation. */
+int matinv_whiten_batched(int dtype, int q, int npoint, const void *dC, size_t strideC, const void *dM, const void *dX, void *dW, void *dMaha,
+                          void *dLogdet, void *dLogpdf, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a whiten request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_whiten_kernel_name(int dtype, int q);
+/* Host-pointer form (hM, `info` and each output optional; hX is read only with hW, hMaha or hLogpdf). Synchronous. */
+int matinv_whiten_batched_host(int dtype, int q, int npoint, const void *hC, size_t strideC, const void *hM, const void *hX, void *hW,
+                               void *hMaha, void *hLogdet, void *hLogpdf, size_t batch, int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
