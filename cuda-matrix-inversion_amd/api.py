@@ -931,6 +931,124 @@ def whiten_kernel_name(dtype, q: int) -> str:
     return _lib.lib().matinv_whiten_kernel_name(code, q).decode()
 
 
+_MULTI_TARGET_OUTPUTS = ("alpha", "quad", "logdet", "logml", "mean")
+
+
+def multi_target_batched(n, Bs, Cs, Ys, As=None, alpha=None, quad=None, logdet=None, logml=None, mean=None, batchSize=None, info=None,
+                         want=_MULTI_TARGET_OUTPUTS, ntarget=None, nquery=None):
+    """Multi-output GP solves on device tensors (matinv_multi_target_batched; asynchronous on torch's current stream): D target vectors and
+    Q query points per covariance matrix, one factorisation. With M_k = B_k + diag c_k:
+        alpha[k, t] = M_k^-1 y_kt,  quad[k, t] = y_kt^T alpha[k, t],  logdet[k] = log det M_k,
+        logml[k, t] = -(quad[k, t] + logdet[k] + n log 2 pi) / 2,  mean[k, t, j] = a_kj^T alpha[k, t]
+    Ys: batchSize*D*n elements, target (k, t) at (k*D + t)*n; alpha has its layout. As: batchSize*Q*n elements as in predict_batched. quad
+    and logml are batchSize*D, logdet batchSize, mean batchSize*D*Q with element (k, t, j) at (k*D + t)*Q + j. D and Q are inferred from
+    Ys.numel() and As.numel() unless `ntarget` / `nquery` are given.
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one; which are asked for
+    changes no bit of the others. "mean" in the default `want` is dropped when As is None. Cs may be None (M = B); Ys may be None when only
+    logdet is asked for. Only B's lower triangle is read and no input is modified. Not positive definite: info = the 1-based column of
+    the first non-positive pivot and every requested output of that matrix NaN.
+    Returns (alpha, quad, logdet, logml, mean), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Ys, As, alpha, quad, logdet, logml, mean, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    unknown = set(want) - set(_MULTI_TARGET_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_MULTI_TARGET_OUTPUTS}")
+    if want is _MULTI_TARGET_OUTPUTS and As is None:
+        want = _MULTI_TARGET_OUTPUTS[:-1]
+    given = dict(alpha=alpha, quad=quad, logdet=logdet, logml=logml, mean=mean)
+    asked = {k: given[k] is not None or k in want for k in _MULTI_TARGET_OUTPUTS}
+    if not any(asked.values()):
+        raise ValueError("no output requested")
+    targets = asked["alpha"] or asked["quad"] or asked["logml"] or asked["mean"]
+    if targets and Ys is None:
+        raise ValueError("alpha, quad, logml and mean need the targets Ys")
+    if asked["mean"] and As is None:
+        raise ValueError("mean needs the cross-covariance vectors As")
+    if not targets:
+        ntarget = 0
+    elif ntarget is None:
+        ntarget = Ys.numel() // (batchSize * n) if batchSize else 0
+    if not asked["mean"]:
+        nquery = 0
+    elif nquery is None:
+        nquery = As.numel() // (batchSize * n) if batchSize else 0
+    if targets and batchSize and (ntarget < 1 or Ys.numel() < batchSize * ntarget * n):
+        raise ValueError("Ys needs batchSize*D*n elements, D >= 1")
+    if asked["mean"] and batchSize and (nquery < 1 or As.numel() < batchSize * nquery * n):
+        raise ValueError("As needs batchSize*Q*n elements, Q >= 1")
+    sizes = dict(alpha=batchSize * ntarget * n, quad=batchSize * ntarget, logdet=batchSize, logml=batchSize * ntarget,
+                 mean=batchSize * ntarget * nquery)
+    for k in _MULTI_TARGET_OUTPUTS:
+        if asked[k] and given[k] is None:
+            given[k] = torch.empty(sizes[k], dtype=Bs.dtype, device=Bs.device)
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ys, As, *given.values())):
+        raise TypeError("Bs, Cs, Ys, As and the outputs must have one dtype")
+    if (Cs is not None and Cs.numel() < batchSize * n) or \
+            any(given[k] is not None and given[k].numel() < sizes[k] for k in _MULTI_TARGET_OUTPUTS):
+        raise ValueError("Cs needs batchSize*n elements, alpha batchSize*D*n, quad and logml batchSize*D, logdet batchSize, "
+                         "mean batchSize*D*Q")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_multi_target_batched(
+            _torch_dtype_code(Bs), n, ntarget, nquery, p(Bs), p(Cs), p(Ys) if targets else None, p(As) if asked["mean"] else None,
+            p(given["alpha"]), p(given["quad"]), p(given["logdet"]), p(given["logml"]), p(given["mean"]), batchSize, p(info),
+            _stream_ptr(Bs)))
+    return given["alpha"], given["quad"], given["logdet"], given["logml"], given["mean"]
+
+
+def multi_target_batched_host(n, Bs: np.ndarray, Cs, Ys, As=None, want=_MULTI_TARGET_OUTPUTS, ntarget=None, nquery=None):
+    """matinv_multi_target_batched_host on numpy batches (packed; Cs may be None, Ys may be None when only "logdet" is in want, As may be
+    None without "mean" in want, which the default `want` then drops): returns (alpha, quad, logdet, logml, mean, info), None for the
+    outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Cs, Ys, As = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Ys, As))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ys, As)):
+        raise TypeError("Bs, Cs, Ys and As must have one dtype")
+    if want is _MULTI_TARGET_OUTPUTS and As is None:
+        want = _MULTI_TARGET_OUTPUTS[:-1]
+    unknown = set(want) - set(_MULTI_TARGET_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_MULTI_TARGET_OUTPUTS}")
+    batch = Bs.size // (n * n)
+    targets = bool(set(want) - {"logdet"})
+    if targets and Ys is None:
+        raise ValueError("alpha, quad, logml and mean need the targets Ys")
+    if "mean" in want and As is None:
+        raise ValueError("mean needs the cross-covariance vectors As")
+    if not targets:
+        ntarget = 0
+    elif ntarget is None:
+        ntarget = Ys.size // (batch * n) if batch else 0
+    if "mean" not in want:
+        nquery = 0
+    elif nquery is None:
+        nquery = As.size // (batch * n) if batch else 0
+    if targets and batch and (ntarget < 1 or Ys.size < batch * ntarget * n):
+        raise ValueError("Ys needs batch*D*n elements, D >= 1")
+    if "mean" in want and batch and (nquery < 1 or As.size < batch * nquery * n):
+        raise ValueError("As needs batch*Q*n elements, Q >= 1")
+    if Cs is not None and Cs.size < batch * n:
+        raise ValueError("Cs smaller than batch*n")
+    sizes = dict(alpha=batch * ntarget * n, quad=batch * ntarget, logdet=batch, logml=batch * ntarget, mean=batch * ntarget * nquery)
+    out = {k: np.empty(sizes[k], dtype=Bs.dtype) if k in want else None for k in _MULTI_TARGET_OUTPUTS}
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_multi_target_batched_host(
+        _np_dtype_code(Bs.dtype), n, ntarget, nquery, p(Bs), p(Cs), p(Ys) if targets else None, p(As) if "mean" in want else None,
+        p(out["alpha"]), p(out["quad"]), p(out["logdet"]), p(out["logml"]), p(out["mean"]), batch, p(info)))
+    return out["alpha"], out["quad"], out["logdet"], out["logml"], out["mean"], info
+
+
+def multi_target_kernel_name(dtype, n: int) -> str:
+    """matinv_multi_target_kernel_name: the kernel a multi-target request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_multi_target_kernel_name(code, n).decode()
+
+
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")
 
 

@@ -1344,6 +1344,86 @@ int whiten_host(int q, int npoint, const void *hC, size_t strideC, const void *h
     return MATINV_OK;
 }
 
+// ---- batched multi-output GP solves: many target vectors per covariance matrix (matinv_multi_target_batched) ---------------------------
+// the checks of predict_check_args, in its order
+int multi_target_check_args(int dtype, int n, int ntarget, int nquery, const void *dBs, const void *dYs, const void *dAs, const void *dAlpha,
+                            const void *dQuad, const void *dLogdet, const void *dLogml, const void *dMean, size_t batch)
+{
+    const bool targets = dAlpha || dQuad || dLogml || dMean;
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (targets && ntarget < 1) return fail(MATINV_ERR_ARG, "ntarget must be >= 1 with alpha, quad, logml or mean (got %d)", ntarget);
+    if (dMean && nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 with mean (got %d)", nquery);
+    if (!dBs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!targets && !dLogdet) return fail(MATINV_ERR_ARG, "no output requested (alpha, quad, logdet, logml and mean are all null)");
+    if (targets && !dYs) return fail(MATINV_ERR_ARG, "alpha, quad, logml or mean requested without the targets (dYs is null)");
+    if (dMean && !dAs) return fail(MATINV_ERR_ARG, "mean requested without the query vectors (dAs is null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    if (targets && ntarget > 1024) return fail(MATINV_ERR_UNSUPPORTED, "ntarget=%d exceeds the limit of 1024 targets per call", ntarget);
+    if (dMean && nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
+    return MATINV_OK;
+}
+
+// n <= 96: the multi-target form of the one-wavefront SPD sweep. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
+template <class T>
+int multi_target_dispatch(int n, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dYs, const void *dAs, void *dAlpha,
+                          void *dQuad, void *dLogdet, void *dLogml, void *dMean, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *y = static_cast<const T *>(dYs);
+    const T *a = static_cast<const T *>(dAs);
+    T *al = static_cast<T *>(dAlpha), *qd = static_cast<T *>(dQuad), *ld = static_cast<T *>(dLogdet), *lm = static_cast<T *>(dLogml);
+    T *mn = static_cast<T *>(dMean);
+    const hipError_t e = multi_target_tile_supports(n)
+                             ? launch_multi_target_tile<T>(n, ntarget, nquery, B, c, y, a, al, qd, ld, lm, mn, batch, dInfo, stream)
+                             : launch_multi_target_global<T>(n, ntarget, nquery, B, c, y, a, al, qd, ld, lm, mn, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "multi_target launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int multi_target_host(int n, int ntarget, int nquery, const void *hBs, const void *hCs, const void *hYs, const void *hAs, void *hAlpha,
+                      void *hQuad, void *hLogdet, void *hLogml, void *hMean, size_t batch, int *info)
+{
+    const bool targets = hAlpha || hQuad || hLogml || hMean;
+    const size_t vec = (size_t)n * batch, mat = vec * n, ts = targets ? batch * (size_t)ntarget : 0, ys = ts * n;
+    const size_t qs = hMean ? batch * (size_t)nquery : 0, ms = hMean ? ts * (size_t)nquery : 0;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dY = nullptr, *dA = nullptr, *dAl = nullptr, *dQd = nullptr, *dLd = nullptr, *dLm = nullptr;
+    T *dMn = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess && targets) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
+    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dA), qs * (size_t)n * sizeof(T));
+    if (e == hipSuccess && hAlpha) e = staging_alloc(reinterpret_cast<void **>(&dAl), ys * sizeof(T));
+    if (e == hipSuccess && hQuad) e = staging_alloc(reinterpret_cast<void **>(&dQd), ts * sizeof(T));
+    if (e == hipSuccess && hLogdet) e = staging_alloc(reinterpret_cast<void **>(&dLd), batch * sizeof(T));
+    if (e == hipSuccess && hLogml) e = staging_alloc(reinterpret_cast<void **>(&dLm), ts * sizeof(T));
+    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMn), ms * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dY) e = hipMemcpy(dY, hYs, ys * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && dA) e = hipMemcpy(dA, hAs, qs * (size_t)n * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = multi_target_dispatch<T>(n, ntarget, nquery, dB, dC, dY, dA, dAl, dQd, dLd, dLm, dMn, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hAlpha) e = hipMemcpy(hAlpha, dAl, ys * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hQuad) e = hipMemcpy(hQuad, dQd, ts * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hLogdet) e = hipMemcpy(hLogdet, dLd, batch * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hLogml) e = hipMemcpy(hLogml, dLm, ts * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMn, ms * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dY), staging_free(dA), staging_free(dAl), staging_free(dQd), staging_free(dLd);
+    staging_free(dLm), staging_free(dMn), staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "multi_target host<->device");
+    return MATINV_OK;
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -1895,6 +1975,34 @@ int matinv_whiten_batched_host(int dtype, int q, int npoint, const void *hC, siz
     if (rc != MATINV_OK || batch == 0) return rc;
     if (dtype == MATINV_F64) return whiten_host<double>(q, npoint, hC, strideC, hM, hX, hW, hMaha, hLogdet, hLogpdf, batch, info);
     return whiten_host<float>(q, npoint, hC, strideC, hM, hX, hW, hMaha, hLogdet, hLogpdf, batch, info);
+}
+
+int matinv_multi_target_batched(int dtype, int n, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dYs, const void *dAs,
+                                void *dAlpha, void *dQuad, void *dLogdet, void *dLogml, void *dMean, size_t batch, int *dInfo, void *stream)
+{
+    int rc = multi_target_check_args(dtype, n, ntarget, nquery, dBs, dYs, dAs, dAlpha, dQuad, dLogdet, dLogml, dMean, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64)
+        return multi_target_dispatch<double>(n, ntarget, nquery, dBs, dCs, dYs, dAs, dAlpha, dQuad, dLogdet, dLogml, dMean, batch, dInfo, st);
+    return multi_target_dispatch<float>(n, ntarget, nquery, dBs, dCs, dYs, dAs, dAlpha, dQuad, dLogdet, dLogml, dMean, batch, dInfo, st);
+}
+
+const char *matinv_multi_target_kernel_name(int dtype, int n)
+{
+    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return multi_target_tile_supports(n) ? name_multi_target_tile(dtype == MATINV_F64, n) : name_multi_target_global(dtype == MATINV_F64);
+}
+
+int matinv_multi_target_batched_host(int dtype, int n, int ntarget, int nquery, const void *hBs, const void *hCs, const void *hYs,
+                                     const void *hAs, void *hAlpha, void *hQuad, void *hLogdet, void *hLogml, void *hMean, size_t batch,
+                                     int *info)
+{
+    int rc = multi_target_check_args(dtype, n, ntarget, nquery, hBs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64)
+        return multi_target_host<double>(n, ntarget, nquery, hBs, hCs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch, info);
+    return multi_target_host<float>(n, ntarget, nquery, hBs, hCs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch, info);
 }
 
 int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs,

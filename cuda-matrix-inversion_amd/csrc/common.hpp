@@ -447,6 +447,22 @@ hipError_t launch_whiten_global(int n, int npoint, const T *Cs, size_t stride, c
                                 size_t batch, int *info, hipStream_t stream);
 const char *name_whiten_global(bool f64);
 
+// Multi-output GP solves (matinv_multi_target_batched): Bs, Cs as for the prediction; Ys: batch * ntarget * n, target t of matrix k a run
+// of n elements at (k ntarget + t) n; As: batch * nquery * n as for the prediction; Al: as Ys, M^-1 y_t; Qd: batch * ntarget, y_t^T M^-1 y_t;
+// Ld: batch, log det M; Lm: batch * ntarget, -1/2 (quad + logdet + n log 2 pi); Mn: batch * ntarget * nquery, element (k, t, j) at
+// (k ntarget + t) nquery + j. Every output is optional; Ys is read with every output but Ld, As with Mn only.
+// (a) the multi-target form of the one-wavefront SPD sweep, n <= 96 (multi_target_tile_kernels.hip, multi_target_tile_f32_kernels.hip)
+bool multi_target_tile_supports(int n);
+template <class T>
+hipError_t launch_multi_target_tile(int n, int ntarget, int nquery, const T *Bs, const T *Cs, const T *Ys, const T *As, T *Al, T *Qd, T *Ld,
+                                    T *Lm, T *Mn, size_t batch, int *info, hipStream_t stream);
+const char *name_multi_target_tile(bool f64, int n);
+// (b) the multi-target form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_multi_target_global(int n, int ntarget, int nquery, const T *Bs, const T *Cs, const T *Ys, const T *As, T *Al, T *Qd,
+                                      T *Ld, T *Lm, T *Mn, size_t batch, int *info, hipStream_t stream);
+const char *name_multi_target_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

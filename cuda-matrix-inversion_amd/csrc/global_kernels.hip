@@ -1153,4 +1153,132 @@ const char *name_whiten_global(bool f64)
                : "matinv_chol_global<float, true, true, true, true, true, true, true>";
 }
 
+// ---- multi-output GP solves, 96 < n <= 1024 (matinv_multi_target_batched behind multi_target_tile_impl.hpp) -----------------------------
+// The multi-target form of matinv_chol_global: one more template argument again ("Multi-output solves"). M = B + diag c is
+// factored in the matrix's slice of library scratch, as above. Thread 0 folds the diagonal of L into a PivotProduct: logdet = 2 log prod
+// L_ii. Then one thread per target, on the target's own n elements of scratch behind the factor: v = y; columns k ascending:
+// w_k = v_k / L_kk, quad += w_k^2, v_i -= L_ik w_k for i > k; then rows k descending: alpha_k = (w_k - sum_{i > k} L_ik alpha_i) / L_kk,
+// i ascending. Then one thread per (target, query) pair: mean = sum_i a_j[i] alpha_t[i], i ascending. The order of operations of a
+// target knows nothing of D or of its position, that of a pair nothing of Q either. Not SPD: info = the failing column + 1 and every
+// requested output NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x; `per` elements
+// of workspace each (n^2, and n ntarget more when the targets are read).
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR, bool WHITEN, bool MULTI>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Ys, const T *As, int ntarget, int nquery,
+                                                                 T *Al, T *Qd, T *Ld, T *Lm, T *Mn, int *info, int n, T *workspace,
+                                                                 size_t per, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR && WHITEN && MULTI, "the nine-argument form is the multi-target kernel");
+    __shared__ T col[1024];
+    __shared__ T s_ld;
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    const bool targets = Al || Qd || Lm || Mn;  // block-uniform
+    const size_t nn = (size_t)n * n, nd = targets ? (size_t)ntarget : 0, nq = Mn ? (size_t)nquery : 0;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *V = W + nn;
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        if (Al)
+            for (size_t e = t; e < nd * n; e += GL_THREADS) Al[k_mat * nd * n + e] = nan_of<T>();
+        for (size_t s = t; s < nd; s += GL_THREADS) {
+            if (Qd) Qd[k_mat * nd + s] = nan_of<T>();
+            if (Lm) Lm[k_mat * nd + s] = nan_of<T>();
+        }
+        if (Mn)
+            for (size_t e = t; e < nd * nq; e += GL_THREADS) Mn[k_mat * nd * nq + e] = nan_of<T>();
+        if (Ld && t == 0) Ld[k_mat] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    if (t == 0) {
+        PivotProduct<T> prod;
+        for (int i = 0; i < n; ++i) prod.fold(W[(size_t)i * n + i]);
+        const T ld = (T)2 * prod.log_value();
+        s_ld = ld;
+        if (Ld) Ld[k_mat] = ld;
+    }
+    __syncthreads();
+    const T ld = s_ld;
+    for (size_t s = t; s < nd; s += GL_THREADS) {
+        const T *y = Ys + (k_mat * nd + s) * n;
+        T *v = V + s * n;
+        for (int i = 0; i < n; ++i) v[i] = y[i];
+        T qd = 0;
+        for (int k = 0; k < n; ++k) {
+            const T *lk = W + (size_t)k * n;
+            const T w = v[k] / lk[k];
+            v[k] = w;
+            qd += w * w;
+            for (int i = k + 1; i < n; ++i) v[i] -= lk[i] * w;
+        }
+        for (int k = n - 1; k >= 0; --k) {
+            const T *lk = W + (size_t)k * n;
+            T a = v[k];
+            for (int i = k + 1; i < n; ++i) a -= lk[i] * v[i];
+            v[k] = a / lk[k];
+        }
+        if (Al)
+            for (int i = 0; i < n; ++i) Al[(k_mat * nd + s) * n + i] = v[i];
+        if (Qd) Qd[k_mat * nd + s] = qd;
+        // log 2 pi
+        if (Lm) Lm[k_mat * nd + s] = (T)-0.5 * ((qd + ld) + (T)n * (T)1.83787706640934548356);
+    }
+    if (Mn) {  // block-uniform
+        __syncthreads();  // every target's alpha is in V
+        for (size_t e = t; e < nd * nq; e += GL_THREADS) {
+            const size_t s = e / nq, j = e - s * nq;
+            const T *a = As + (k_mat * nq + j) * n, *v = V + s * n;
+            T m = 0;
+            for (int i = 0; i < n; ++i) m += a[i] * v[i];
+            Mn[k_mat * nd * nq + e] = m;
+        }
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_multi_target_global(int n, int ntarget, int nquery, const T *Bs, const T *Cs, const T *Ys, const T *As, T *Al, T *Qd,
+                                      T *Ld, T *Lm, T *Mn, size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk, each with its n x D block of targets, fit the blocked-path workspace cap (launch_loo_global)
+    const size_t per = (size_t)n * n + ((Al || Qd || Lm || Mn) ? (size_t)n * ntarget : 0);
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0,
+                           stream, Bs, Cs, Ys, As, ntarget, nquery, Al, Qd, Ld, Lm, Mn, info, n, ws, per, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_multi_target_global<double>(int, int, int, const double *, const double *, const double *, const double *,
+                                                       double *, double *, double *, double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_multi_target_global<float>(int, int, int, const float *, const float *, const float *, const float *, float *,
+                                                      float *, float *, float *, float *, size_t, int *, hipStream_t);
+
+const char *name_multi_target_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true, true, true>";
+}
+
 }  // namespace matinv

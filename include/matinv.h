@@ -345,6 +345,37 @@ const char *matinv_whiten_kernel_name(int dtype, int q);
 int matinv_whiten_batched_host(int dtype, int q, int npoint, const void *hC, size_t strideC, const void *hM, const void *hX, void *hW,
                                void *hMaha, void *hLogdet, void *hLogpdf, size_t batch, int *info);
 
+/* Multi-output GP solves, device-resident: ntarget target vectors y_kt and nquery query points per covariance matrix. With
+ * M_k = B_k + diag(c_k) and a_kj as in matinv_predict_batched:
+ *   alpha[(k*ntarget + t)*n + i]           = (M_k^-1 y_kt)_i                          the layout of dYs
+ *   quad[k*ntarget + t]                    = y_kt^T M_k^-1 y_kt
+ *   logdet[k]                              = log det M_k
+ *   logml[k*ntarget + t]                   = -1/2 (quad + logdet + n log 2 pi)        the log marginal likelihood of target t
+ *   mean[(k*ntarget + t)*nquery + j]       = a_kj^T alpha_kt                          for ntarget = 1 the layout of matinv_predict_batched
+ * dBs, dCs, dAs as in matinv_predict_batched (only the lower triangle of B read; dCs may be NULL). dYs: batch*ntarget*n elements, target t
+ * of matrix k the run of n elements at (k*ntarget + t)*n. Every output is optional and at least one is required (all NULL:
+ * MATINV_ERR_ARG); which of them are requested does not change a bit of the others. dYs and ntarget >= 1 are needed for every output but
+ * dLogdet: with dLogdet alone ntarget may be 0 and dYs NULL. dAs and nquery >= 1 are needed with dMean only: without it nquery may be 0,
+ * dAs NULL, and dAs is not read. 1 <= n <= 1024, ntarget <= 1024, nquery <= 1024 (beyond: MATINV_ERR_UNSUPPORTED, after the pointer
+ * checks); batch < 2^31; batch == 0 is a no-op after the dtype and n checks. No input is modified (outputs must not overlap inputs);
+ * neither M, its inverse nor its factor is written to caller memory. Bit for bit, logdet_k depends on matrix k alone, alpha, quad and
+ * logml of (k, t) on matrix k and target t alone, and mean of (k, t, j) additionally on query j alone -- not on batch, ntarget, nquery
+ * or the position of t or j. dInfo (optional): 0, or the 1-based column of the first non-positive (or NaN) pivot -- every requested
+ * output of that matrix is then NaN; there is no fallback launch. n <= 96: the multi-target form of the one-wavefront SPD tile sweep;
+ * the targets in groups of 16 on the MFMA unit, T = M^-1 Y kept in registers and multiplied with every group of 16 queries
+ * (n^2/2 + n + ntarget n + ceil(ntarget / 16) nquery n elements read, ntarget n + 2 ntarget + 1 + ntarget nquery written). Beyond, to
+ * n = 1024: the multi-target form of the global-memory Cholesky kernel on a working copy of n (n + ntarget) elements per matrix in
+ * library scratch (k-range chunks under MATINV_BLOCKED_WS_MB), one thread per target. Asynchronous, no host synchronisation. */
+int matinv_multi_target_batched(int dtype, int n, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dYs, const void *dAs,
+                                void *dAlpha, void *dQuad, void *dLogdet, void *dLogml, void *dMean, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a multi-target request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_multi_target_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional; hYs is read with every output but hLogdet, hAs only with hMean).
+ * Synchronous. */
+int matinv_multi_target_batched_host(int dtype, int n, int ntarget, int nquery, const void *hBs, const void *hCs, const void *hYs,
+                                     const void *hAs, void *hAlpha, void *hQuad, void *hLogdet, void *hLogml, void *hMean, size_t batch,
+                                     int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
