@@ -1049,6 +1049,112 @@ def multi_target_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_multi_target_kernel_name(code, n).decode()
 
 
+_MULTI_TARGET_GRAD_OUTPUTS = ("grad", "gradc", "logml", "alpha")
+
+
+def multi_target_grad_batched(n, Bs, Cs, Ys, dMs, grad=None, gradc=None, logml=None, alpha=None, batchSize=None, info=None, want=("grad",),
+                              ntarget=None, nparam=None):
+    """Gradients of the multi-output GP log marginal likelihood on device tensors (matinv_multi_target_grad_batched; asynchronous on torch's
+    current stream): the gradient of sum_t logml[k, t] of multi_target_batched, from one factorisation. With M_k = B_k + diag c_k,
+    K = M_k^-1, alpha_t = K y_kt for the D targets and G = sum_t alpha_t alpha_t^T - D K:
+        grad[k, p] = 1/2 sum_ij G_ij dM_p[i, j],  gradc[k, i] = 1/2 G_ii,  logml[k, t] and alpha[k, t] as multi_target_batched (bit for bit)
+    Ys: batchSize*D*n elements, target (k, t) at (k*D + t)*n; alpha has its layout. dMs: batchSize*P*n*n elements, matrix (k, p) at
+    (k*P + p)*n*n, column-major, lower triangle read. grad is batchSize*P, gradc batchSize*n, logml batchSize*D. D and P are inferred from
+    Ys.numel() and dMs.numel() unless `ntarget` / `nparam` are given.
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one; which are asked for
+    changes no bit of the others. Cs may be None (M = B), dMs may be None when grad is not asked for. Only the lower triangles of B and
+    dM are read and no input is modified. Not positive definite: info = the 1-based column of the first non-positive pivot and every
+    requested output of that matrix NaN.
+    Returns (grad, gradc, logml, alpha), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Ys, dMs, grad, gradc, logml, alpha, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    unknown = set(want) - set(_MULTI_TARGET_GRAD_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_MULTI_TARGET_GRAD_OUTPUTS}")
+    given = dict(grad=grad, gradc=gradc, logml=logml, alpha=alpha)
+    asked = {k: given[k] is not None or k in want for k in _MULTI_TARGET_GRAD_OUTPUTS}
+    if not any(asked.values()):
+        raise ValueError("no output requested")
+    if Ys is None:
+        raise ValueError("every output needs the targets Ys")
+    if asked["grad"] and dMs is None:
+        raise ValueError("grad needs the derivative matrices dMs")
+    if ntarget is None:
+        ntarget = Ys.numel() // (batchSize * n) if batchSize else 0
+    if not asked["grad"]:
+        nparam = 0
+    elif nparam is None:
+        nparam = dMs.numel() // (batchSize * n * n) if batchSize else 0
+    if batchSize and (ntarget < 1 or Ys.numel() < batchSize * ntarget * n):
+        raise ValueError("Ys needs batchSize*D*n elements, D >= 1")
+    if asked["grad"] and batchSize and (nparam < 1 or dMs.numel() < batchSize * nparam * n * n):
+        raise ValueError("dMs needs batchSize*P*n*n elements, P >= 1")
+    sizes = dict(grad=batchSize * nparam, gradc=batchSize * n, logml=batchSize * ntarget, alpha=batchSize * ntarget * n)
+    for k in _MULTI_TARGET_GRAD_OUTPUTS:
+        if asked[k] and given[k] is None:
+            given[k] = torch.empty(sizes[k], dtype=Bs.dtype, device=Bs.device)
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ys, dMs, *given.values())):
+        raise TypeError("Bs, Cs, Ys, dMs and the outputs must have one dtype")
+    if (Cs is not None and Cs.numel() < batchSize * n) or \
+            any(given[k] is not None and given[k].numel() < sizes[k] for k in _MULTI_TARGET_GRAD_OUTPUTS):
+        raise ValueError("Cs needs batchSize*n elements, grad batchSize*P, gradc batchSize*n, logml batchSize*D, alpha batchSize*D*n")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_multi_target_grad_batched(
+            _torch_dtype_code(Bs), n, ntarget, nparam, p(Bs), p(Cs), p(Ys), p(dMs) if asked["grad"] else None, p(given["grad"]),
+            p(given["gradc"]), p(given["logml"]), p(given["alpha"]), batchSize, p(info), _stream_ptr(Bs)))
+    return given["grad"], given["gradc"], given["logml"], given["alpha"]
+
+
+def multi_target_grad_batched_host(n, Bs: np.ndarray, Cs, Ys, dMs, want=_MULTI_TARGET_GRAD_OUTPUTS, ntarget=None, nparam=None):
+    """matinv_multi_target_grad_batched_host on numpy batches (packed; Cs may be None, dMs may be None without "grad" in want, which the
+    default `want` then drops): returns (grad, gradc, logml, alpha, info), None for the outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Cs, Ys, dMs = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Ys, dMs))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Ys, dMs)):
+        raise TypeError("Bs, Cs, Ys and dMs must have one dtype")
+    if want is _MULTI_TARGET_GRAD_OUTPUTS and dMs is None:
+        want = _MULTI_TARGET_GRAD_OUTPUTS[1:]
+    unknown = set(want) - set(_MULTI_TARGET_GRAD_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_MULTI_TARGET_GRAD_OUTPUTS}")
+    batch = Bs.size // (n * n)
+    if Ys is None:
+        raise ValueError("every output needs the targets Ys")
+    if "grad" in want and dMs is None:
+        raise ValueError("grad needs the derivative matrices dMs")
+    if ntarget is None:
+        ntarget = Ys.size // (batch * n) if batch else 0
+    if "grad" not in want:
+        nparam = 0
+    elif nparam is None:
+        nparam = dMs.size // (batch * n * n) if batch else 0
+    if batch and (ntarget < 1 or Ys.size < batch * ntarget * n):
+        raise ValueError("Ys needs batch*D*n elements, D >= 1")
+    if "grad" in want and batch and (nparam < 1 or dMs.size < batch * nparam * n * n):
+        raise ValueError("dMs needs batch*P*n*n elements, P >= 1")
+    if Cs is not None and Cs.size < batch * n:
+        raise ValueError("Cs smaller than batch*n")
+    sizes = dict(grad=batch * nparam, gradc=batch * n, logml=batch * ntarget, alpha=batch * ntarget * n)
+    out = {k: np.empty(sizes[k], dtype=Bs.dtype) if k in want else None for k in _MULTI_TARGET_GRAD_OUTPUTS}
+    info = np.zeros(batch, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_multi_target_grad_batched_host(
+        _np_dtype_code(Bs.dtype), n, ntarget, nparam, p(Bs), p(Cs), p(Ys), p(dMs) if "grad" in want else None, p(out["grad"]),
+        p(out["gradc"]), p(out["logml"]), p(out["alpha"]), batch, p(info)))
+    return out["grad"], out["gradc"], out["logml"], out["alpha"], info
+
+
+def multi_target_grad_kernel_name(dtype, n: int) -> str:
+    """matinv_multi_target_grad_kernel_name: the kernel a multi-target gradient request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_multi_target_grad_kernel_name(code, n).decode()
+
+
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")
 
 

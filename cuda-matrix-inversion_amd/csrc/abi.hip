@@ -1424,6 +1424,82 @@ int multi_target_host(int n, int ntarget, int nquery, const void *hBs, const voi
     return MATINV_OK;
 }
 
+// ---- gradients of the multi-output GP log marginal likelihood (matinv_multi_target_grad_batched) ---------------------------------------
+// the checks of multi_target_check_args, in its order; every output needs the targets
+int multi_target_grad_check_args(int dtype, int n, int ntarget, int nparam, const void *dBs, const void *dYs, const void *dDMs,
+                                 const void *dGrad, const void *dGradC, const void *dLogml, const void *dAlpha, size_t batch)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (batch == 0) return MATINV_OK;
+    if (ntarget < 1) return fail(MATINV_ERR_ARG, "ntarget must be >= 1 (got %d)", ntarget);
+    if (nparam < 0 || (dGrad && nparam < 1)) return fail(MATINV_ERR_ARG, "nparam must be >= 1 with grad, >= 0 without (got %d)", nparam);
+    if (!dBs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dGrad && !dGradC && !dLogml && !dAlpha) return fail(MATINV_ERR_ARG, "no output requested (grad, gradc, logml and alpha are all null)");
+    if (!dYs) return fail(MATINV_ERR_ARG, "the targets are needed for every output (dYs is null)");
+    if (dGrad && !dDMs) return fail(MATINV_ERR_ARG, "grad requested without derivative matrices (dDMs is null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    if (ntarget > 1024) return fail(MATINV_ERR_UNSUPPORTED, "ntarget=%d exceeds the limit of 1024 targets per call", ntarget);
+    if (dGrad && nparam > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nparam=%d exceeds the limit of 1024 derivative matrices per call", nparam);
+    return MATINV_OK;
+}
+
+// n <= 96: the gradient form of the multi-target tile kernels. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
+template <class T>
+int multi_target_grad_dispatch(int n, int ntarget, int nparam, const void *dBs, const void *dCs, const void *dYs, const void *dDMs,
+                               void *dGrad, void *dGradC, void *dLogml, void *dAlpha, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *y = static_cast<const T *>(dYs);
+    const T *dM = dGrad ? static_cast<const T *>(dDMs) : nullptr;  // not read without grad
+    T *grad = static_cast<T *>(dGrad), *gradc = static_cast<T *>(dGradC), *lm = static_cast<T *>(dLogml), *al = static_cast<T *>(dAlpha);
+    const hipError_t e =
+        multi_target_grad_tile_supports(n)
+            ? launch_multi_target_grad_tile<T>(n, ntarget, nparam, B, c, y, dM, grad, gradc, lm, al, batch, dInfo, stream)
+            : launch_multi_target_grad_global<T>(n, ntarget, nparam, B, c, y, dM, grad, gradc, lm, al, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "multi_target_grad launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int multi_target_grad_host(int n, int ntarget, int nparam, const void *hBs, const void *hCs, const void *hYs, const void *hDMs, void *hGrad,
+                           void *hGradC, void *hLogml, void *hAlpha, size_t batch, int *info)
+{
+    const size_t vec = (size_t)n * batch, mat = vec * n, ts = batch * (size_t)ntarget, ys = ts * n;
+    const size_t par = hGrad ? batch * (size_t)nparam : 0;
+    int rc = check_device();
+    if (rc) return rc;
+    T *dB = nullptr, *dC = nullptr, *dY = nullptr, *dDM = nullptr, *dGrad = nullptr, *dGradC = nullptr, *dLm = nullptr, *dAl = nullptr;
+    int *dInfo = nullptr;
+    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
+    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
+    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
+    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dDM), par * (size_t)n * n * sizeof(T));
+    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dGrad), par * sizeof(T));
+    if (e == hipSuccess && hGradC) e = staging_alloc(reinterpret_cast<void **>(&dGradC), vec * sizeof(T));
+    if (e == hipSuccess && hLogml) e = staging_alloc(reinterpret_cast<void **>(&dLm), ts * sizeof(T));
+    if (e == hipSuccess && hAlpha) e = staging_alloc(reinterpret_cast<void **>(&dAl), ys * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dY, hYs, ys * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && hGrad) e = hipMemcpy(dDM, hDMs, par * (size_t)n * n * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        rc = multi_target_grad_dispatch<T>(n, ntarget, nparam, dB, dC, dY, dDM, dGrad, dGradC, dLm, dAl, batch, dInfo, nullptr);
+    if (e == hipSuccess && rc == MATINV_OK && hGrad) e = hipMemcpy(hGrad, dGrad, par * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hGradC) e = hipMemcpy(hGradC, dGradC, vec * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hLogml) e = hipMemcpy(hLogml, dLm, ts * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && hAlpha) e = hipMemcpy(hAlpha, dAl, ys * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    staging_free(dB), staging_free(dC), staging_free(dY), staging_free(dDM), staging_free(dGrad), staging_free(dGradC), staging_free(dLm);
+    staging_free(dAl), staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "multi_target_grad host<->device");
+    return MATINV_OK;
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -2003,6 +2079,35 @@ int matinv_multi_target_batched_host(int dtype, int n, int ntarget, int nquery, 
     if (dtype == MATINV_F64)
         return multi_target_host<double>(n, ntarget, nquery, hBs, hCs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch, info);
     return multi_target_host<float>(n, ntarget, nquery, hBs, hCs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch, info);
+}
+
+int matinv_multi_target_grad_batched(int dtype, int n, int ntarget, int nparam, const void *dBs, const void *dCs, const void *dYs,
+                                     const void *dDMs, void *dGrad, void *dGradC, void *dLogml, void *dAlpha, size_t batch, int *dInfo,
+                                     void *stream)
+{
+    int rc = multi_target_grad_check_args(dtype, n, ntarget, nparam, dBs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64)
+        return multi_target_grad_dispatch<double>(n, ntarget, nparam, dBs, dCs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, batch, dInfo, st);
+    return multi_target_grad_dispatch<float>(n, ntarget, nparam, dBs, dCs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, batch, dInfo, st);
+}
+
+const char *matinv_multi_target_grad_kernel_name(int dtype, int n)
+{
+    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return multi_target_grad_tile_supports(n) ? name_multi_target_grad_tile(dtype == MATINV_F64, n)
+                                              : name_multi_target_grad_global(dtype == MATINV_F64);
+}
+
+int matinv_multi_target_grad_batched_host(int dtype, int n, int ntarget, int nparam, const void *hBs, const void *hCs, const void *hYs,
+                                          const void *hDMs, void *hGrad, void *hGradC, void *hLogml, void *hAlpha, size_t batch, int *info)
+{
+    int rc = multi_target_grad_check_args(dtype, n, ntarget, nparam, hBs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64)
+        return multi_target_grad_host<double>(n, ntarget, nparam, hBs, hCs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch, info);
+    return multi_target_grad_host<float>(n, ntarget, nparam, hBs, hCs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch, info);
 }
 
 int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs,

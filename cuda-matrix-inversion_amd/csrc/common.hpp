@@ -463,6 +463,21 @@ hipError_t launch_multi_target_global(int n, int ntarget, int nquery, const T *B
                                       T *Ld, T *Lm, T *Mn, size_t batch, int *info, hipStream_t stream);
 const char *name_multi_target_global(bool f64);
 
+// Gradients of the multi-output log marginal likelihood (matinv_multi_target_grad_batched): Bs, Cs, Ys as above, dMs as for
+// matinv_logml_grad_batched; grad: batch * nparam, gradc: batch * n, Lm: batch * ntarget, Al: as Ys. Every output is optional; dMs is read
+// with grad only.
+// (a) the gradient form of the multi-target tile kernels, n <= 96 (multi_target_grad_tile_kernels.hip, multi_target_grad_tile_f32_kernels.hip)
+bool multi_target_grad_tile_supports(int n);
+template <class T>
+hipError_t launch_multi_target_grad_tile(int n, int ntarget, int nparam, const T *Bs, const T *Cs, const T *Ys, const T *dMs, T *grad,
+                                         T *gradc, T *Lm, T *Al, size_t batch, int *info, hipStream_t stream);
+const char *name_multi_target_grad_tile(bool f64, int n);
+// (b) the multi-target gradient form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_multi_target_grad_global(int n, int ntarget, int nparam, const T *Bs, const T *Cs, const T *Ys, const T *dMs, T *grad,
+                                           T *gradc, T *Lm, T *Al, size_t batch, int *info, hipStream_t stream);
+const char *name_multi_target_grad_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

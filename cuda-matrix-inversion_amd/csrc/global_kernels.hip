@@ -1281,4 +1281,180 @@ const char *name_multi_target_global(bool f64)
                : "matinv_chol_global<float, true, true, true, true, true, true, true, true>";
 }
 
+// ---- gradients of the multi-output log marginal likelihood, 96 < n <= 1024 (matinv_multi_target_grad_batched behind
+// multi_target_grad_tile_impl.hpp) ------------------------------------------------------------------------------------------------------
+// The multi-target gradient form of matinv_chol_global: one more template argument again ("Gradients of the multi-output log
+// marginal likelihood"). The factorisation, the diagonal fold and the one-thread-per-target substitutions are those of the multi-target
+// form above, so logml and alpha are its values; alpha_t stays in the target's n elements of scratch behind the factor. Then, when grad
+// or gradc is asked for, L <- L^-1 and K over it in place as in the gradient form, and with G_rc = sum_t alpha_tr alpha_tc - D K_rc
+// formed on the fly (t ascending):
+//     gradc_i = 1/2 G_ii,   grad_p = sum_{r >= c} w_rc G_rc dM_p[r][c],  w = 1/2 on the diagonal, 1 below
+// grad_p summed per thread in element order, then on the fixed LDS tree. Not SPD: info = the failing column + 1 and every requested
+// output NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x; `per` = n (n + ntarget)
+// elements of workspace each.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR, bool WHITEN, bool MULTI, bool MTGRAD>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Ys, const T *dMs, int ntarget, int nparam,
+                                                                 T *grad, T *gradc, T *Lm, T *Al, int *info, int n, T *workspace, size_t per,
+                                                                 size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR && WHITEN && MULTI && MTGRAD,
+                  "the ten-argument form is the multi-target gradient kernel");
+    __shared__ T col[1024];
+    __shared__ T s_ld;
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    const size_t nn = (size_t)n * n, nd = (size_t)ntarget;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *V = W + nn;
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        if (Al)
+            for (size_t e = t; e < nd * n; e += GL_THREADS) Al[k_mat * nd * n + e] = nan_of<T>();
+        if (Lm)
+            for (size_t s = t; s < nd; s += GL_THREADS) Lm[k_mat * nd + s] = nan_of<T>();
+        if (gradc)
+            for (int i = t; i < n; i += GL_THREADS) gradc[k_mat * n + i] = nan_of<T>();
+        if (grad)
+            for (int p = t; p < nparam; p += GL_THREADS) grad[k_mat * nparam + p] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    if (t == 0) {
+        PivotProduct<T> prod;
+        for (int i = 0; i < n; ++i) prod.fold(W[(size_t)i * n + i]);
+        s_ld = (T)2 * prod.log_value();
+    }
+    __syncthreads();
+    const T ld = s_ld;
+    for (size_t s = t; s < nd; s += GL_THREADS) {
+        const T *y = Ys + (k_mat * nd + s) * n;
+        T *v = V + s * n;
+        for (int i = 0; i < n; ++i) v[i] = y[i];
+        T qd = 0;
+        for (int k = 0; k < n; ++k) {
+            const T *lk = W + (size_t)k * n;
+            const T w = v[k] / lk[k];
+            v[k] = w;
+            qd += w * w;
+            for (int i = k + 1; i < n; ++i) v[i] -= lk[i] * w;
+        }
+        for (int k = n - 1; k >= 0; --k) {
+            const T *lk = W + (size_t)k * n;
+            T a = v[k];
+            for (int i = k + 1; i < n; ++i) a -= lk[i] * v[i];
+            v[k] = a / lk[k];
+        }
+        if (Al)
+            for (int i = 0; i < n; ++i) Al[(k_mat * nd + s) * n + i] = v[i];
+        // log 2 pi
+        if (Lm) Lm[k_mat * nd + s] = (T)-0.5 * ((qd + ld) + (T)n * (T)1.83787706640934548356);
+    }
+    if (grad || gradc) {  // block-uniform
+        __syncthreads();  // every target's alpha is in V, and the factor is no longer needed
+        for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+            const T ajj = (T)1 / W[(size_t)j * n + j];
+            for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+            __syncthreads();
+            for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+                T s = 0;
+                for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+                W[(size_t)j * n + i] = -s * ajj;
+            }
+            if (t == 0) W[(size_t)j * n + j] = ajj;
+            __syncthreads();
+        }
+        // column c of K over column c of L^-1; the columns beyond c are still those of L^-1
+        for (int c = 0; c < n; ++c) {
+            for (int k = c + t; k < n; k += GL_THREADS) col[k] = W[(size_t)c * n + k];
+            __syncthreads();
+            for (int r = c + t; r < n; r += GL_THREADS) {
+                T s = 0;
+                if (r == c) {
+                    for (int k = r; k < n; ++k) s += col[k] * col[k];
+                } else {
+                    for (int k = r; k < n; ++k) s += W[(size_t)r * n + k] * col[k];
+                }
+                W[(size_t)c * n + r] = s;
+            }
+            __syncthreads();
+        }
+        const T dscale = (T)ntarget;
+        if (gradc)
+            for (int i = t; i < n; i += GL_THREADS) {
+                T aa = 0;
+                for (size_t s = 0; s < nd; ++s) aa += V[s * n + i] * V[s * n + i];
+                gradc[k_mat * n + i] = (T)0.5 * (aa - dscale * W[(size_t)i * n + i]);
+            }
+        if (grad) {
+            for (int p = 0; p < nparam; ++p) {
+                const T *D = dMs + (k_mat * nparam + p) * nn;
+                T s = 0;
+                for (size_t e = t; e < nn; e += GL_THREADS) {
+                    const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+                    if (r < c) continue;
+                    T aa = 0;
+                    for (size_t u = 0; u < nd; ++u) aa += V[u * n + r] * V[u * n + c];
+                    const T g = aa - dscale * W[e];
+                    s += (r == c ? (T)0.5 : (T)1) * g * D[e];
+                }
+                // block sum on a fixed tree
+                col[t] = s;
+                __syncthreads();
+                for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+                    if (t < off) col[t] += col[t + off];
+                    __syncthreads();
+                }
+                if (t == 0) grad[k_mat * nparam + p] = col[0];
+                __syncthreads();
+            }
+        }
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_multi_target_grad_global(int n, int ntarget, int nparam, const T *Bs, const T *Cs, const T *Ys, const T *dMs, T *grad,
+                                           T *gradc, T *Lm, T *Al, size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk, each with its n x D block of targets, fit the blocked-path workspace cap (launch_loo_global)
+    const size_t per = (size_t)n * n + (size_t)n * ntarget;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true, true, true, true>), dim3((unsigned)cnt),
+                           dim3(GL_THREADS), 0, stream, Bs, Cs, Ys, dMs, ntarget, nparam, grad, gradc, Lm, Al, info, n, ws, per, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_multi_target_grad_global<double>(int, int, int, const double *, const double *, const double *, const double *,
+                                                            double *, double *, double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_multi_target_grad_global<float>(int, int, int, const float *, const float *, const float *, const float *, float *,
+                                                           float *, float *, float *, size_t, int *, hipStream_t);
+
+const char *name_multi_target_grad_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true>";
+}
+
 }  // namespace matinv

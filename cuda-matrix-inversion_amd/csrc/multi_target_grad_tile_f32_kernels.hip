@@ -1,0 +1,10 @@
+// multi_target_grad_tile_f32_kernels.hip -- fp32 instantiation of the one-wavefront multi-target gradient tile kernels
+// (multi_target_grad_tile_impl.hpp); a translation unit of its own so that the two precisions compile in parallel
+#include "multi_target_grad_tile_impl.hpp"
+
+namespace matinv {
+
+template hipError_t launch_multi_target_grad_tile<float>(int, int, int, const float *, const float *, const float *, const float *, float *,
+                                                         float *, float *, float *, size_t, int *, hipStream_t);
+
+}  // namespace matinv

@@ -376,6 +376,36 @@ int matinv_multi_target_batched_host(int dtype, int n, int ntarget, int nquery, 
                                      const void *hAs, void *hAlpha, void *hQuad, void *hLogdet, void *hLogml, void *hMean, size_t batch,
                                      int *info);
 
+/* Gradients of the multi-output GP log marginal likelihood, device-resident: the gradient of sum_t logml_kt of
+ * matinv_multi_target_batched, from one factorisation. With M_k = B_k + diag(c_k), K = M_k^-1, D = ntarget targets y_kt,
+ * alpha_t = K y_kt, P = nparam symmetric derivative matrices dM_p per matrix and G = sum_t alpha_t alpha_t^T - D K:
+ *   grad[k*nparam + p]            = 1/2 sum_ij G_ij dM_p[i][j]                   d(sum_t logml_t) / d theta_p
+ *   gradc[k*n + i]                = 1/2 G_ii                                     d(sum_t logml_t) / d c_i
+ *   logml[k*ntarget + t]          = -1/2 (y_t^T K y_t + log det M + n log 2 pi)  as matinv_multi_target_batched
+ *   alpha[(k*ntarget + t)*n + i]  = (alpha_t)_i                                  the layout of dYs
+ * dBs, dCs, dYs as in matinv_multi_target_batched (only the lower triangle of B read; dCs may be NULL); dDMs as in
+ * matinv_logml_grad_batched (matrix (k, p) at (k*nparam + p)*n*n, only its lower triangle read). Every output is optional and at least
+ * one is required (all NULL: MATINV_ERR_ARG); which of them are requested does not change a bit of the others. dGrad needs nparam >= 1
+ * and dDMs; without it nparam may be 0, dDMs NULL, and dDMs is not read. ntarget >= 1 and dYs are always needed. 1 <= n <= 1024,
+ * ntarget <= 1024, nparam <= 1024 (beyond: MATINV_ERR_UNSUPPORTED, after the pointer checks); batch < 2^31; batch == 0 is a no-op after
+ * the dtype and n checks. No input is modified (outputs must not overlap inputs); neither M, its inverse nor its factor is written to
+ * caller memory. logml and alpha carry the bits matinv_multi_target_batched gives for the same inputs. dInfo (optional): 0, or the
+ * 1-based column of the first non-positive (or NaN) pivot -- every requested output of that matrix is then NaN; there is no fallback
+ * launch. n <= 96: the gradient form of the multi-target tile sweep: the targets in groups of 16 on the MFMA unit, then
+ * G accumulated over -D K in the registers by rank-16 MFMA updates and contracted with each dM_p streamed once
+ * (n^2/2 + n + ntarget n + nparam n^2/2 elements read, nparam + n + ntarget + ntarget n written; with ntarget > 16 alpha is read back
+ * once, from dAlpha or from ntarget n elements of library scratch per workgroup). Beyond, to n = 1024: the multi-target gradient form of
+ * the global-memory Cholesky kernel on a working copy of n (n + ntarget) elements per matrix in library scratch (k-range chunks under
+ * MATINV_BLOCKED_WS_MB). Asynchronous, no host synchronisation. */
+int matinv_multi_target_grad_batched(int dtype, int n, int ntarget, int nparam, const void *dBs, const void *dCs, const void *dYs,
+                                     const void *dDMs, void *dGrad, void *dGradC, void *dLogml, void *dAlpha, size_t batch, int *dInfo,
+                                     void *stream);
+/* Name of the __global__ function a multi-target gradient request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_multi_target_grad_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional; hDMs is read only with hGrad). Synchronous. */
+int matinv_multi_target_grad_batched_host(int dtype, int n, int ntarget, int nparam, const void *hBs, const void *hCs, const void *hYs,
+                                          const void *hDMs, void *hGrad, void *hGradC, void *hLogml, void *hAlpha, size_t batch, int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
