@@ -1155,6 +1155,134 @@ def multi_target_grad_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_multi_target_grad_kernel_name(code, n).decode()
 
 
+_TREND_OUTPUTS = ("beta", "covbeta", "alpha", "quad", "logml", "mean", "var")
+_TREND_TARGET_OUTPUTS = ("beta", "alpha", "quad", "logml", "mean")
+
+
+def _trend_plan(n, batch, want, given, numel, Ys, As, Gs, Es, Hs, nbasis, ntarget, nquery):
+    """what a trend request computes and its counts: (asked, nbasis, ntarget, nquery, sizes); `numel` counts a tensor's or array's elements"""
+    unknown = set(want) - set(_TREND_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_TREND_OUTPUTS}")
+    if want is _TREND_OUTPUTS:  # the default: what the inputs given allow
+        want = tuple(k for k in _TREND_OUTPUTS if not ((k in _TREND_TARGET_OUTPUTS and Ys is None)
+                                                        or (k in ("mean", "var") and (As is None or Gs is None)) or (k == "var" and Es is None)))
+    asked = {k: given[k] is not None or k in want for k in _TREND_OUTPUTS}
+    if not any(asked.values()):
+        raise ValueError("no output requested")
+    targets = any(asked[k] for k in _TREND_TARGET_OUTPUTS)
+    queries = asked["mean"] or asked["var"]
+    if Hs is None:
+        raise ValueError("the basis vectors Hs are needed")
+    if targets and Ys is None:
+        raise ValueError("beta, alpha, quad, logml and mean need the targets Ys")
+    if queries and (As is None or Gs is None):
+        raise ValueError("mean and var need the cross-covariance vectors As and the basis values Gs")
+    if asked["var"] and Es is None:
+        raise ValueError("var needs the prior variances Es")
+    if nbasis is None:
+        nbasis = numel(Hs) // (batch * n) if batch else 1
+    if not 1 <= nbasis <= 16 or nbasis > n:
+        raise ValueError(f"nbasis must be in 1 .. min(16, n) (got {nbasis})")
+    if not targets:
+        ntarget = 0
+    elif ntarget is None:
+        ntarget = numel(Ys) // (batch * n) if batch else 0
+    if not queries:
+        nquery = 0
+    elif nquery is None:
+        nquery = numel(As) // (batch * n) if batch else 0
+    if batch and numel(Hs) < batch * nbasis * n:
+        raise ValueError("Hs needs batch*K*n elements")
+    if targets and batch and (ntarget < 1 or numel(Ys) < batch * ntarget * n):
+        raise ValueError("Ys needs batch*D*n elements, D >= 1")
+    if queries and batch and (nquery < 1 or numel(As) < batch * nquery * n or numel(Gs) < batch * nquery * nbasis):
+        raise ValueError("As needs batch*Q*n elements and Gs batch*Q*K, Q >= 1")
+    if asked["var"] and numel(Es) < batch * nquery:
+        raise ValueError("Es needs batch*Q elements")
+    sizes = dict(beta=batch * ntarget * nbasis, covbeta=batch * nbasis * nbasis, alpha=batch * ntarget * n, quad=batch * ntarget,
+                 logml=batch * ntarget, mean=batch * ntarget * nquery, var=batch * nquery)
+    return asked, nbasis, ntarget, nquery, sizes
+
+
+def trend_batched(n, Bs, Cs, Hs, Ys=None, As=None, Gs=None, Es=None, beta=None, covbeta=None, alpha=None, quad=None, logml=None, mean=None,
+                  var=None, batchSize=None, info=None, want=_TREND_OUTPUTS, nbasis=None, ntarget=None, nquery=None):
+    """GP regression with a linear trend (universal kriging) on device tensors (matinv_trend_batched; asynchronous on torch's current
+    stream): K basis vectors, D targets and Q query points per covariance matrix, one factorisation. With M_k = B_k + diag c_k,
+    Kinv = M_k^-1, H = [h_1 .. h_K] and A = H^T Kinv H:
+        beta[k, t] = A^-1 H^T Kinv y_kt,  covbeta[k] = A^-1,  alpha[k, t] = Kinv (y_kt - H beta[k, t]),  quad[k, t] = y_kt^T alpha[k, t],
+        logml[k, t] = -(quad[k, t] + log det M_k + log det A + (n - K) log 2 pi) / 2,
+        mean[k, t, j] = a_kj^T alpha[k, t] + g_kj^T beta[k, t],
+        var[k, j] = e_kj - a_kj^T Kinv a_kj + r^T A^-1 r,  r = g_kj - H^T Kinv a_kj
+    Hs: batchSize*K*n elements, basis vector (k, b) at (k*K + b)*n; Ys, As as in multi_target_batched; Gs: batchSize*Q*K, element
+    (k, j, b) at (k*Q + j)*K + b; Es: batchSize*Q. beta is batchSize*D*K, covbeta batchSize*K*K, alpha has the layout of Ys, quad and logml
+    are batchSize*D, mean batchSize*D*Q with element (k, t, j) at (k*D + t)*Q + j, var batchSize*Q. K, D and Q are inferred from
+    Hs.numel(), Ys.numel() and As.numel() unless `nbasis` / `ntarget` / `nquery` are given; 1 <= K <= min(16, n).
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one; which are asked for
+    changes no bit of the others. The default `want` holds every output the inputs given allow: those of the targets need Ys, mean and var
+    need As and Gs, var needs Es. Cs may be None (M = B). Only B's lower triangle is read and no input is modified. info = the 1-based
+    column of the first non-positive pivot of M, or n + b for the first non-positive pivot b of A (H rank deficient); every requested
+    output of that matrix is then NaN.
+    Returns (beta, covbeta, alpha, quad, logml, mean, var), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Hs, Ys, As, Gs, Es, beta, covbeta, alpha, quad, logml, mean, var, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    given = dict(beta=beta, covbeta=covbeta, alpha=alpha, quad=quad, logml=logml, mean=mean, var=var)
+    asked, nbasis, ntarget, nquery, sizes = _trend_plan(n, batchSize, want, given, lambda t: t.numel(), Ys, As, Gs, Es, Hs, nbasis, ntarget,
+                                                        nquery)
+    for k in _TREND_OUTPUTS:
+        if asked[k] and given[k] is None:
+            given[k] = torch.empty(sizes[k], dtype=Bs.dtype, device=Bs.device)
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Hs, Ys, As, Gs, Es, *given.values())):
+        raise TypeError("Bs, Cs, Hs, Ys, As, Gs, Es and the outputs must have one dtype")
+    if (Cs is not None and Cs.numel() < batchSize * n) or any(given[k] is not None and given[k].numel() < sizes[k] for k in _TREND_OUTPUTS):
+        raise ValueError("Cs needs batchSize*n elements, beta batchSize*D*K, covbeta batchSize*K*K, alpha batchSize*D*n, quad and logml "
+                         "batchSize*D, mean batchSize*D*Q, var batchSize*Q")
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
+        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    targets = any(asked[k] for k in _TREND_TARGET_OUTPUTS)
+    queries = asked["mean"] or asked["var"]
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_trend_batched(
+            _torch_dtype_code(Bs), n, nbasis, ntarget, nquery, p(Bs), p(Cs), p(Hs), p(Ys) if targets else None, p(As) if queries else None,
+            p(Gs) if queries else None, p(Es) if asked["var"] else None, *(p(given[k]) for k in _TREND_OUTPUTS), batchSize, p(info),
+            _stream_ptr(Bs)))
+    return tuple(given[k] for k in _TREND_OUTPUTS)
+
+
+def trend_batched_host(n, Bs: np.ndarray, Cs, Hs, Ys=None, As=None, Gs=None, Es=None, want=_TREND_OUTPUTS, nbasis=None, ntarget=None,
+                       nquery=None):
+    """matinv_trend_batched_host on numpy batches (packed; Cs may be None; Ys, As, Gs, Es may be None when no output in want needs them, and
+    the default `want` holds what the inputs given allow): returns (beta, covbeta, alpha, quad, logml, mean, var, info), None for the
+    outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Cs, Hs, Ys, As, Gs, Es = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Hs, Ys, As, Gs, Es))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Hs, Ys, As, Gs, Es)):
+        raise TypeError("Bs, Cs, Hs, Ys, As, Gs and Es must have one dtype")
+    batch = Bs.size // (n * n)
+    none = dict.fromkeys(_TREND_OUTPUTS)
+    asked, nbasis, ntarget, nquery, sizes = _trend_plan(n, batch, want, none, lambda a: a.size, Ys, As, Gs, Es, Hs, nbasis, ntarget, nquery)
+    if Cs is not None and Cs.size < batch * n:
+        raise ValueError("Cs smaller than batch*n")
+    out = {k: np.empty(sizes[k], dtype=Bs.dtype) if asked[k] else None for k in _TREND_OUTPUTS}
+    info = np.zeros(batch, dtype=np.int32)
+    targets = any(asked[k] for k in _TREND_TARGET_OUTPUTS)
+    queries = asked["mean"] or asked["var"]
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    _lib.check(_lib.lib().matinv_trend_batched_host(
+        _np_dtype_code(Bs.dtype), n, nbasis, ntarget, nquery, p(Bs), p(Cs), p(Hs), p(Ys) if targets else None, p(As) if queries else None,
+        p(Gs) if queries else None, p(Es) if asked["var"] else None, *(p(out[k]) for k in _TREND_OUTPUTS), batch, p(info)))
+    return (*(out[k] for k in _TREND_OUTPUTS), info)
+
+
+def trend_kernel_name(dtype, n: int) -> str:
+    """matinv_trend_kernel_name: the kernel a trend request launches ("" when the request would be refused)."""
+    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    return _lib.lib().matinv_trend_kernel_name(code, n).decode()
+
+
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")
 
 

@@ -1500,6 +1500,94 @@ int multi_target_grad_host(int n, int ntarget, int nparam, const void *hBs, cons
     return MATINV_OK;
 }
 
+// ---- batched GP regression with a linear trend (matinv_trend_batched) --------------------------------------------------------------------
+// the checks of multi_target_check_args, in its order; the basis count is checked with n and dtype, before the empty batch returns
+int trend_check_args(int dtype, int n, int nbasis, int ntarget, int nquery, const void *dBs, const void *dHs, const void *dYs, const void *dAs,
+                     const void *dGs, const void *dEs, const void *dBeta, const void *dCovBeta, const void *dAlpha, const void *dQuad,
+                     const void *dLogml, const void *dMean, const void *dVar, size_t batch)
+{
+    const bool targets = dBeta || dAlpha || dQuad || dLogml || dMean, queries = dMean || dVar;
+    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (nbasis < 1 || nbasis > 16) return fail(MATINV_ERR_ARG, "nbasis must be in 1 .. 16 (got %d)", nbasis);
+    if (nbasis > n) return fail(MATINV_ERR_ARG, "nbasis=%d exceeds n=%d: H^T M^-1 H would be singular", nbasis, n);
+    if (batch == 0) return MATINV_OK;
+    if (targets && ntarget < 1) return fail(MATINV_ERR_ARG, "ntarget must be >= 1 with beta, alpha, quad, logml or mean (got %d)", ntarget);
+    if (queries && nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 with mean or var (got %d)", nquery);
+    if (!dBs || !dHs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!targets && !dCovBeta && !dVar)
+        return fail(MATINV_ERR_ARG, "no output requested (beta, covbeta, alpha, quad, logml, mean and var are all null)");
+    if (targets && !dYs) return fail(MATINV_ERR_ARG, "beta, alpha, quad, logml or mean requested without the targets (dYs is null)");
+    if (queries && !dAs) return fail(MATINV_ERR_ARG, "mean or var requested without the query vectors (dAs is null)");
+    if (queries && !dGs) return fail(MATINV_ERR_ARG, "mean or var requested without the basis values of the queries (dGs is null)");
+    if (dVar && !dEs) return fail(MATINV_ERR_ARG, "var requested without the prior variances (dEs is null)");
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
+    if (targets && ntarget > 1024) return fail(MATINV_ERR_UNSUPPORTED, "ntarget=%d exceeds the limit of 1024 targets per call", ntarget);
+    if (queries && nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
+    return MATINV_OK;
+}
+
+// n <= 96: the trend form of the one-wavefront SPD sweep. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
+template <class T>
+int trend_dispatch(int n, int nbasis, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dHs, const void *dYs,
+                   const void *dAs, const void *dGs, const void *dEs, void *dBeta, void *dCovBeta, void *dAlpha, void *dQuad, void *dLogml,
+                   void *dMean, void *dVar, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *h = static_cast<const T *>(dHs);
+    const T *y = static_cast<const T *>(dYs), *a = static_cast<const T *>(dAs), *g = static_cast<const T *>(dGs);
+    const T *e0 = static_cast<const T *>(dEs);
+    T *be = static_cast<T *>(dBeta), *cb = static_cast<T *>(dCovBeta), *al = static_cast<T *>(dAlpha), *qd = static_cast<T *>(dQuad);
+    T *lm = static_cast<T *>(dLogml), *mn = static_cast<T *>(dMean), *vr = static_cast<T *>(dVar);
+    const hipError_t e =
+        trend_tile_supports(n)
+            ? launch_trend_tile<T>(n, nbasis, ntarget, nquery, B, c, h, y, a, g, e0, be, cb, al, qd, lm, mn, vr, batch, dInfo, stream)
+            : launch_trend_global<T>(n, nbasis, ntarget, nquery, B, c, h, y, a, g, e0, be, cb, al, qd, lm, mn, vr, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "trend launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int trend_host(int n, int nbasis, int ntarget, int nquery, const void *hBs, const void *hCs, const void *hHs, const void *hYs,
+               const void *hAs, const void *hGs, const void *hEs, void *hBeta, void *hCovBeta, void *hAlpha, void *hQuad, void *hLogml,
+               void *hMean, void *hVar, size_t batch, int *info)
+{
+    const bool targets = hBeta || hAlpha || hQuad || hLogml || hMean, queries = hMean || hVar;
+    const size_t K = (size_t)nbasis, vec = (size_t)n * batch, mat = vec * n, ts = targets ? batch * (size_t)ntarget : 0;
+    const size_t qs = queries ? batch * (size_t)nquery : 0;
+    // element counts, in the order of the pointer tables below
+    const size_t in_count[7] = {mat, hCs ? vec : 0, vec * K, ts * n, qs * n, qs * K, hVar ? qs : 0};
+    const size_t out_count[7] = {ts * K, batch * K * K, ts * n, ts, ts, hMean ? ts * (size_t)nquery : 0, qs};
+    const void *const in_host[7] = {hBs, hCs, hHs, targets ? hYs : nullptr, queries ? hAs : nullptr, queries ? hGs : nullptr,
+                                    hVar ? hEs : nullptr};
+    void *const out_host[7] = {hBeta, hCovBeta, hAlpha, hQuad, hLogml, hMean, hVar};
+    int rc = check_device();
+    if (rc) return rc;
+    T *din[7] = {}, *dout[7] = {};
+    int *dInfo = nullptr;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 7 && e == hipSuccess; ++i)
+        if (in_host[i]) e = staging_alloc(reinterpret_cast<void **>(&din[i]), in_count[i] * sizeof(T));
+    for (int i = 0; i < 7 && e == hipSuccess; ++i)
+        if (out_host[i]) e = staging_alloc(reinterpret_cast<void **>(&dout[i]), out_count[i] * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    for (int i = 0; i < 7 && e == hipSuccess; ++i)
+        if (din[i]) e = hipMemcpy(din[i], in_host[i], in_count[i] * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        rc = trend_dispatch<T>(n, nbasis, ntarget, nquery, din[0], din[1], din[2], din[3], din[4], din[5], din[6], dout[0], dout[1], dout[2],
+                               dout[3], dout[4], dout[5], dout[6], batch, dInfo, nullptr);
+    for (int i = 0; i < 7 && e == hipSuccess && rc == MATINV_OK; ++i)
+        if (dout[i]) e = hipMemcpy(out_host[i], dout[i], out_count[i] * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    for (int i = 0; i < 7; ++i) staging_free(din[i]), staging_free(dout[i]);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, "trend host<->device");
+    return MATINV_OK;
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -2108,6 +2196,41 @@ int matinv_multi_target_grad_batched_host(int dtype, int n, int ntarget, int npa
     if (dtype == MATINV_F64)
         return multi_target_grad_host<double>(n, ntarget, nparam, hBs, hCs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch, info);
     return multi_target_grad_host<float>(n, ntarget, nparam, hBs, hCs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch, info);
+}
+
+int matinv_trend_batched(int dtype, int n, int nbasis, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dHs,
+                         const void *dYs, const void *dAs, const void *dGs, const void *dEs, void *dBeta, void *dCovBeta, void *dAlpha,
+                         void *dQuad, void *dLogml, void *dMean, void *dVar, size_t batch, int *dInfo, void *stream)
+{
+    int rc = trend_check_args(dtype, n, nbasis, ntarget, nquery, dBs, dHs, dYs, dAs, dGs, dEs, dBeta, dCovBeta, dAlpha, dQuad, dLogml, dMean,
+                              dVar, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == MATINV_F64)
+        return trend_dispatch<double>(n, nbasis, ntarget, nquery, dBs, dCs, dHs, dYs, dAs, dGs, dEs, dBeta, dCovBeta, dAlpha, dQuad, dLogml,
+                                      dMean, dVar, batch, dInfo, st);
+    return trend_dispatch<float>(n, nbasis, ntarget, nquery, dBs, dCs, dHs, dYs, dAs, dGs, dEs, dBeta, dCovBeta, dAlpha, dQuad, dLogml, dMean,
+                                 dVar, batch, dInfo, st);
+}
+
+const char *matinv_trend_kernel_name(int dtype, int n)
+{
+    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    return trend_tile_supports(n) ? name_trend_tile(dtype == MATINV_F64, n) : name_trend_global(dtype == MATINV_F64);
+}
+
+int matinv_trend_batched_host(int dtype, int n, int nbasis, int ntarget, int nquery, const void *hBs, const void *hCs, const void *hHs,
+                              const void *hYs, const void *hAs, const void *hGs, const void *hEs, void *hBeta, void *hCovBeta, void *hAlpha,
+                              void *hQuad, void *hLogml, void *hMean, void *hVar, size_t batch, int *info)
+{
+    int rc = trend_check_args(dtype, n, nbasis, ntarget, nquery, hBs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml, hMean,
+                              hVar, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    if (dtype == MATINV_F64)
+        return trend_host<double>(n, nbasis, ntarget, nquery, hBs, hCs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml,
+                                  hMean, hVar, batch, info);
+    return trend_host<float>(n, nbasis, ntarget, nquery, hBs, hCs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml, hMean,
+                             hVar, batch, info);
 }
 
 int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs,

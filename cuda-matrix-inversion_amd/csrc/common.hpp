@@ -478,6 +478,25 @@ hipError_t launch_multi_target_grad_global(int n, int ntarget, int nparam, const
                                            T *gradc, T *Lm, T *Al, size_t batch, int *info, hipStream_t stream);
 const char *name_multi_target_grad_global(bool f64);
 
+// GP regression with a linear trend (matinv_trend_batched): Bs, Cs, Ys, As as for the multi-output solves; Hs: batch * nbasis * n, basis
+// vector b of matrix k a run of n elements at (k nbasis + b) n; Gs: batch * nquery * nbasis, the basis values of query j at
+// (k nquery + j) nbasis; Es: batch * nquery. Be: batch * ntarget * nbasis; Cb: batch * nbasis^2; Al: as Ys; Qd, Lm: batch * ntarget;
+// Mn: batch * ntarget * nquery; Vr: batch * nquery. Every output is optional; Ys is read with Be, Al, Qd, Lm, Mn, As and Gs with Mn and Vr,
+// Es with Vr.
+// (a) the trend form of the one-wavefront SPD sweep, n <= 96 (trend_tile_kernels.hip, trend_tile_f32_kernels.hip)
+bool trend_tile_supports(int n);
+template <class T>
+hipError_t launch_trend_tile(int n, int nbasis, int ntarget, int nquery, const T *Bs, const T *Cs, const T *Hs, const T *Ys, const T *As,
+                             const T *Gs, const T *Es, T *Be, T *Cb, T *Al, T *Qd, T *Lm, T *Mn, T *Vr, size_t batch, int *info,
+                             hipStream_t stream);
+const char *name_trend_tile(bool f64, int n);
+// (b) the trend form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_trend_global(int n, int nbasis, int ntarget, int nquery, const T *Bs, const T *Cs, const T *Hs, const T *Ys, const T *As,
+                               const T *Gs, const T *Es, T *Be, T *Cb, T *Al, T *Qd, T *Lm, T *Mn, T *Vr, size_t batch, int *info,
+                               hipStream_t stream);
+const char *name_trend_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

@@ -1457,4 +1457,261 @@ const char *name_multi_target_grad_global(bool f64)
                : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true>";
 }
 
+// ---- GP regression with a linear trend, 96 < n <= 1024 (matinv_trend_batched behind trend_tile_impl.hpp) -------------------------------
+// The trend form of matinv_chol_global: one more template argument again ("Regression with a linear trend"). M = B + diag c
+// is factored in the matrix's slice of library scratch and the diagonal of L folded as in the multi-target form. Then
+//   * one thread per column of [H | Y], on the column's own n elements of scratch behind the factor: forward and backward substitution
+//     as in the multi-target form, which leaves Kinv h_b and Kinv y_t;
+//   * A[b][b'] = h_b^T (Kinv h_b'), b >= b', i ascending, one thread per element, into LDS; thread 0 factors A = L_A L_A^T (K <= 16) and
+//     folds its pivots L_A,bb^2 into a PivotProduct: log det A. A non-positive or NaN pivot b: info = n + b, every requested output NaN.
+//     Thread b solves column b of L_A^-1; covbeta[b][b'] = sum_i L_A^-1[i][b] L_A^-1[i][b'], i ascending from b, stored to both positions;
+//   * one thread per target: (H^T Kinv y)_b = (Kinv h_b)^T y, beta by the two triangular solves, alpha = Kinv y - sum_b (Kinv h_b) beta_b
+//     (b ascending) in place, quad = y^T alpha, logml;
+//   * one thread per (target, query) pair: mean = sum_i a_j[i] alpha_t[i] + sum_b g_j[b] beta_t[b];
+//   * one thread per query: w = L^-1 a_j on n elements of scratch, a^T Kinv a = sum w_k^2; r_b = g_b - (Kinv h_b)^T a_j; z = L_A^-1 r;
+//     var = (e - a^T Kinv a) + sum z_b^2.
+// The order of operations of an output knows nothing of D, Q, or the position of its target or query; the loops over the basis run over
+// the K real vectors only, in ascending order. Correct first; speed is not a goal here. Workgroup blockIdx.x serves matrix
+// first + blockIdx.x; `per` elements of workspace each: n^2 + n (K + D') + K D' + (n + K) Q', D' = D when the targets are read, Q' = Q
+// with var.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR, bool WHITEN, bool MULTI, bool MTGRAD, bool TREND>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Hs, const T *Ys, const T *As, const T *Gs,
+                                                                 const T *Es, int nbasis, int ntarget, int nquery, T *Be, T *Cb, T *Al, T *Qd,
+                                                                 T *Lm, T *Mn, T *Vr, int *info, int n, T *workspace, size_t per, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR && WHITEN && MULTI && MTGRAD && TREND,
+                  "the eleven-argument form is the trend kernel");
+    __shared__ T col[1024];
+    __shared__ T sA[16 * 17], sLi[16 * 17];
+    __shared__ T s_ld, s_ldA;
+    __shared__ int s_abad;
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    const bool targets = Be || Al || Qd || Lm || Mn;  // block-uniform
+    const size_t nn = (size_t)n * n, K = (size_t)nbasis, nd = targets ? (size_t)ntarget : 0;
+    const size_t nq = (Mn || Vr) ? (size_t)nquery : 0, nqv = Vr ? (size_t)nquery : 0;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *V = W + nn;                 // Kinv h_b, b < K, then Kinv y_t -> alpha_t
+    T *Bt = V + (K + nd) * n;      // beta_t
+    T *U = Bt + nd * K;            // L^-1 a_j
+    T *R = U + nqv * n;            // r_j -> z_j
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    __syncthreads();
+    int bad = gl_chol_factor(W, n, col);
+    if (!bad) {  // block-uniform
+        if (t == 0) {
+            PivotProduct<T> prod;
+            for (int i = 0; i < n; ++i) prod.fold(W[(size_t)i * n + i]);
+            s_ld = (T)2 * prod.log_value();
+        }
+        for (size_t s = t; s < K + nd; s += GL_THREADS) {
+            const T *x = s < K ? Hs + (k_mat * K + s) * n : Ys + (k_mat * nd + (s - K)) * n;
+            T *v = V + s * n;
+            for (int i = 0; i < n; ++i) v[i] = x[i];
+            for (int k = 0; k < n; ++k) {
+                const T *lk = W + (size_t)k * n;
+                const T w = v[k] / lk[k];
+                v[k] = w;
+                for (int i = k + 1; i < n; ++i) v[i] -= lk[i] * w;
+            }
+            for (int k = n - 1; k >= 0; --k) {
+                const T *lk = W + (size_t)k * n;
+                T a = v[k];
+                for (int i = k + 1; i < n; ++i) a -= lk[i] * v[i];
+                v[k] = a / lk[k];
+            }
+        }
+        __syncthreads();  // Kinv [H | Y] is in V
+        for (size_t e = t; e < K * K; e += GL_THREADS) {
+            const size_t b = e / K, b2 = e - b * K;
+            if (b < b2) continue;
+            const T *h = Hs + (k_mat * K + b) * n, *v = V + b2 * n;
+            T a = 0;
+            for (int i = 0; i < n; ++i) a += h[i] * v[i];
+            sA[b * 17 + b2] = a;
+        }
+        __syncthreads();
+        if (t == 0) {  // A = L_A L_A^T in place, 1 / L_bb on the diagonal
+            int abad = 0;
+            PivotProduct<T> prod;
+            for (int j = 0; j < nbasis; ++j) {
+                const T d = sA[j * 17 + j];
+                if (!(d > (T)0) && abad == 0) abad = j + 1;
+                prod.fold(d);
+                const T rs = (T)1 / sqrt(d);
+                // the update with the unscaled column and the quotient A[jj][j] / d: a basis vector that repeats an earlier one bit for
+                // bit gets a pivot of exactly 0 (trend_tile_impl.hpp)
+                for (int jj = j + 1; jj < nbasis; ++jj) {
+                    const T m = sA[jj * 17 + j] / d;
+                    for (int i = jj; i < nbasis; ++i) sA[i * 17 + jj] -= sA[i * 17 + j] * m;
+                }
+                sA[j * 17 + j] = rs;
+                for (int i = j + 1; i < nbasis; ++i) sA[i * 17 + j] *= rs;
+            }
+            s_abad = abad;
+            s_ldA = prod.log_value();
+        }
+        __syncthreads();
+        if (s_abad) bad = n + s_abad;
+    }
+    if (bad) {  // block-uniform
+        if (Be)
+            for (size_t e = t; e < nd * K; e += GL_THREADS) Be[k_mat * nd * K + e] = nan_of<T>();
+        if (Cb)
+            for (size_t e = t; e < K * K; e += GL_THREADS) Cb[k_mat * K * K + e] = nan_of<T>();
+        if (Al)
+            for (size_t e = t; e < nd * n; e += GL_THREADS) Al[k_mat * nd * n + e] = nan_of<T>();
+        for (size_t s = t; s < nd; s += GL_THREADS) {
+            if (Qd) Qd[k_mat * nd + s] = nan_of<T>();
+            if (Lm) Lm[k_mat * nd + s] = nan_of<T>();
+        }
+        if (Mn)
+            for (size_t e = t; e < nd * nq; e += GL_THREADS) Mn[k_mat * nd * nq + e] = nan_of<T>();
+        if (Vr)
+            for (size_t e = t; e < nq; e += GL_THREADS) Vr[k_mat * nq + e] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    const T ld = s_ld, ldA = s_ldA;
+    if (Cb) {  // block-uniform
+        if (t < nbasis) {  // column t of L_A^-1
+            for (int i = 0; i < nbasis; ++i) {
+                T s = i == t ? (T)1 : (T)0;
+                for (int k = 0; k < i; ++k) s -= sA[i * 17 + k] * sLi[k * 17 + t];
+                sLi[i * 17 + t] = s * sA[i * 17 + i];
+            }
+        }
+        __syncthreads();
+        for (size_t e = t; e < K * K; e += GL_THREADS) {
+            const size_t b = e / K, b2 = e - b * K;
+            if (b < b2) continue;
+            T a = 0;
+            for (size_t i = b; i < K; ++i) a += sLi[i * 17 + b] * sLi[i * 17 + b2];
+            Cb[k_mat * K * K + b * K + b2] = a;
+            Cb[k_mat * K * K + b2 * K + b] = a;
+        }
+    }
+    for (size_t s = t; s < nd; s += GL_THREADS) {
+        const T *y = Ys + (k_mat * nd + s) * n;
+        T *v = V + (K + s) * n, *be = Bt + s * K;
+        for (size_t b = 0; b < K; ++b) {
+            const T *kh = V + b * n;
+            T a = 0;
+            for (int i = 0; i < n; ++i) a += kh[i] * y[i];
+            be[b] = a;
+        }
+        for (int i = 0; i < nbasis; ++i) {
+            T a = be[i];
+            for (int k = 0; k < i; ++k) a -= sA[i * 17 + k] * be[k];
+            be[i] = a * sA[i * 17 + i];
+        }
+        for (int i = nbasis - 1; i >= 0; --i) {
+            T a = be[i];
+            for (int k = nbasis - 1; k > i; --k) a -= sA[k * 17 + i] * be[k];
+            be[i] = a * sA[i * 17 + i];
+        }
+        for (size_t b = 0; b < K; ++b) {
+            const T *kh = V + b * n;
+            const T bb = be[b];
+            for (int i = 0; i < n; ++i) v[i] -= kh[i] * bb;
+        }
+        T qd = 0;
+        for (int i = 0; i < n; ++i) qd += y[i] * v[i];
+        if (Be)
+            for (size_t b = 0; b < K; ++b) Be[(k_mat * nd + s) * K + b] = be[b];
+        if (Al)
+            for (int i = 0; i < n; ++i) Al[(k_mat * nd + s) * n + i] = v[i];
+        if (Qd) Qd[k_mat * nd + s] = qd;
+        // log 2 pi
+        if (Lm) Lm[k_mat * nd + s] = (T)-0.5 * ((qd + (ld + ldA)) + (T)(n - nbasis) * (T)1.83787706640934548356);
+    }
+    if (Mn) {  // block-uniform
+        __syncthreads();  // every target's alpha is in V, its beta in Bt
+        for (size_t e = t; e < nd * nq; e += GL_THREADS) {
+            const size_t s = e / nq, j = e - s * nq;
+            const T *a = As + (k_mat * nq + j) * n, *v = V + (K + s) * n, *g = Gs + (k_mat * nq + j) * K, *be = Bt + s * K;
+            T m = 0, mb = 0;
+            for (int i = 0; i < n; ++i) m += a[i] * v[i];
+            for (size_t b = 0; b < K; ++b) mb += g[b] * be[b];
+            Mn[k_mat * nd * nq + e] = m + mb;
+        }
+    }
+    for (size_t j = t; j < nqv; j += GL_THREADS) {
+        const T *a = As + (k_mat * nq + j) * n, *g = Gs + (k_mat * nq + j) * K;
+        T *w = U + j * n, *r = R + j * K;
+        for (size_t b = 0; b < K; ++b) {
+            const T *kh = V + b * n;
+            T s = 0;
+            for (int i = 0; i < n; ++i) s += kh[i] * a[i];
+            r[b] = g[b] - s;
+        }
+        for (int i = 0; i < n; ++i) w[i] = a[i];
+        T aka = 0;
+        for (int k = 0; k < n; ++k) {
+            const T *lk = W + (size_t)k * n;
+            const T x = w[k] / lk[k];
+            aka += x * x;
+            for (int i = k + 1; i < n; ++i) w[i] -= lk[i] * x;
+        }
+        T rar = 0;
+        for (int i = 0; i < nbasis; ++i) {
+            T s = r[i];
+            for (int k = 0; k < i; ++k) s -= sA[i * 17 + k] * r[k];
+            s *= sA[i * 17 + i];
+            r[i] = s;
+            rar += s * s;
+        }
+        Vr[k_mat * nq + j] = (Es[k_mat * nq + j] - aka) + rar;
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_trend_global(int n, int nbasis, int ntarget, int nquery, const T *Bs, const T *Cs, const T *Hs, const T *Ys, const T *As,
+                               const T *Gs, const T *Es, T *Be, T *Cb, T *Al, T *Qd, T *Lm, T *Mn, T *Vr, size_t batch, int *info,
+                               hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_multi_target_global)
+    const size_t nd = (Be || Al || Qd || Lm || Mn) ? (size_t)ntarget : 0, nqv = Vr ? (size_t)nquery : 0, K = (size_t)nbasis;
+    const size_t per = (size_t)n * n + (size_t)n * (K + nd) + K * nd + ((size_t)n + K) * nqv;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true, true, true, true, true>), dim3((unsigned)cnt),
+                           dim3(GL_THREADS), 0, stream, Bs, Cs, Hs, Ys, As, Gs, Es, nbasis, ntarget, nquery, Be, Cb, Al, Qd, Lm, Mn, Vr, info,
+                           n, ws, per, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_trend_global<double>(int, int, int, int, const double *, const double *, const double *, const double *,
+                                                const double *, const double *, const double *, double *, double *, double *, double *,
+                                                double *, double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_trend_global<float>(int, int, int, int, const float *, const float *, const float *, const float *, const float *,
+                                               const float *, const float *, float *, float *, float *, float *, float *, float *, float *,
+                                               size_t, int *, hipStream_t);
+
+const char *name_trend_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true>";
+}
+
 }  // namespace matinv

@@ -406,6 +406,45 @@ const char *matinv_multi_target_grad_kernel_name(int dtype, int n);
 int matinv_multi_target_grad_batched_host(int dtype, int n, int ntarget, int nparam, const void *hBs, const void *hCs, const void *hYs,
                                           const void *hDMs, void *hGrad, void *hGradC, void *hLogml, void *hAlpha, size_t batch, int *info);
 
+/* GP regression with a linear trend (universal kriging; Rasmussen & Williams 2.7, explicit basis functions with a vague prior on the
+ * coefficients), device-resident. Per matrix k: M = B_k + diag(c_k), Kinv = M^-1, K = nbasis basis vectors h_b (H = [h_1 .. h_K], n x K),
+ * D = ntarget targets y_t, Q = nquery queries with cross-covariance a_j, basis values g_j (K) and prior variance e_j. With
+ * A = H^T Kinv H (K x K, positive definite iff H has full column rank):
+ *   beta[(k*D + t)*K + b]      = (A^-1 H^T Kinv y_t)_b                               the generalised-least-squares coefficients
+ *   covbeta[k*K*K + b*K + b']  = (A^-1)_bb'                                          their covariance; bitwise symmetric
+ *   alpha[(k*D + t)*n + i]     = (Kinv (y_t - H beta_t))_i                           the layout of dYs; H^T alpha_t = 0
+ *   quad[k*D + t]              = (y_t - H beta_t)^T Kinv (y_t - H beta_t) = y_t^T alpha_t
+ *   logml[k*D + t]             = -1/2 (quad_t + log det M + log det A + (n - K) log 2 pi)    the restricted likelihood, R&W eq. 2.45
+ *   mean[(k*D + t)*Q + j]      = a_j^T alpha_t + g_j^T beta_t
+ *   var[k*Q + j]               = e_j - a_j^T Kinv a_j + r_j^T A^-1 r_j,  r_j = g_j - H^T Kinv a_j    R&W eq. 2.42; the same for every target
+ * dBs, dCs, dYs, dAs as in matinv_multi_target_batched (only the lower triangle of B read; dCs may be NULL). dHs: batch*K*n elements, basis
+ * vector b of matrix k the run of n elements at (k*K + b)*n (the layout of dYs). dGs: batch*Q*K elements, g_j of matrix k at (k*Q + j)*K.
+ * dEs: batch*Q elements. Every output is optional and at least one is required (all NULL: MATINV_ERR_ARG); which of them are requested
+ * does not change a bit of the others. dBs and dHs are always needed. dYs and ntarget >= 1 are needed with dBeta, dAlpha, dQuad, dLogml or
+ * dMean; dAs, dGs and nquery >= 1 with dMean or dVar; dEs with dVar. What is not needed is not read and may be NULL (its count 0): dCovBeta
+ * alone needs only B, c and H. 1 <= n <= 1024; 1 <= nbasis <= 16 and nbasis <= n (otherwise MATINV_ERR_ARG, checked with n and dtype);
+ * ntarget <= 1024, nquery <= 1024 (beyond: MATINV_ERR_UNSUPPORTED, after the pointer checks); batch < 2^31; batch == 0 is a no-op after
+ * the dtype, n and nbasis checks. No input is modified (outputs must not overlap inputs); neither M, its inverse nor its factor is written
+ * to caller memory. Bit for bit, covbeta_k depends on matrix k and its basis alone, var of (k, j) additionally on query j alone, beta,
+ * alpha, quad and logml of (k, t) on matrix k, its basis and target t alone, mean of (k, t, j) additionally on query j alone -- not on
+ * batch, ntarget, nquery or the position of t or j. dInfo (optional): 0; or the 1-based column of the first non-positive (or NaN) pivot
+ * of M; or n + b for the first non-positive (or NaN) pivot b (1-based) of A, i.e. a basis that is rank deficient to working precision
+ * (the convention matinv_sample_batched uses for cov). On a non-zero info every requested output of that matrix is NaN; there is no
+ * fallback launch. n <= 96: the trend form of the one-wavefront SPD tile sweep: H, the targets and the queries in groups of 16 on the
+ * MFMA unit, Kinv H parked in LDS, A factored inside the wave (n^2/2 + n + K n + D n read; with mean or var (ceil(D / 16) + 1) Q (n + K) + Q
+ * more; K^2 + D K + D n + 2 D + D Q + Q written). Beyond, to n = 1024: the trend form of the global-memory Cholesky kernel on a working
+ * copy per matrix in library scratch (k-range chunks under MATINV_BLOCKED_WS_MB), one thread per column of [H | Y] and per query.
+ * Asynchronous, no host synchronisation. */
+int matinv_trend_batched(int dtype, int n, int nbasis, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dHs,
+                         const void *dYs, const void *dAs, const void *dGs, const void *dEs, void *dBeta, void *dCovBeta, void *dAlpha,
+                         void *dQuad, void *dLogml, void *dMean, void *dVar, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a trend request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_trend_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional; the inputs are read as the device form reads them). Synchronous. */
+int matinv_trend_batched_host(int dtype, int n, int nbasis, int ntarget, int nquery, const void *hBs, const void *hCs, const void *hHs,
+                              const void *hYs, const void *hAs, const void *hGs, const void *hEs, void *hBeta, void *hCovBeta, void *hAlpha,
+                              void *hQuad, void *hLogml, void *hMean, void *hVar, size_t batch, int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
