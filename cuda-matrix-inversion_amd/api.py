@@ -42,6 +42,25 @@ def _torch_dtype_code(t) -> int:
     raise TypeError(f"only float32/float64 batches are supported, got {t.dtype}")
 
 
+def _dtype_code(dtype) -> int:
+    """the *_kernel_name wrappers take a library dtype code or anything numpy reads as a dtype"""
+    return dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+
+
+def _tensor_ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _array_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+
+def _check_info(info, batch, name="batchSize"):
+    import torch
+    if info is not None and (info.dtype != torch.int32 or info.numel() < batch):
+        raise ValueError(f"info must be an int32 tensor with at least `{name}` elements")
+
+
 # ---------------------------------------------------------------------------------------------- host family
 def _call_reference_gpu(name: str, n: int, As: np.ndarray, aInvs: np.ndarray, batchSize: int) -> None:
     if not (isinstance(As, np.ndarray) and isinstance(aInvs, np.ndarray)):
@@ -157,8 +176,7 @@ def inverse_batched(As, n: int, algo: int = ALGO_GAUSS_JORDAN, out=None, info=No
         out = torch.empty_like(As)
     if out.dtype != As.dtype:
         raise TypeError("out dtype differs from input dtype")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batch):
-        raise ValueError("info must be an int32 tensor with at least `batch` elements")
+    _check_info(info, batch, "batch")
     with torch.cuda.device(As.device):
         _lib.check(_lib.lib().matinv_inverse_batched_ex(
             algo, _torch_dtype_code(As), n, ctypes.c_void_p(As.data_ptr()), stride, ctypes.c_void_p(out.data_ptr()),
@@ -234,8 +252,7 @@ def solve_batched(A, B, n: int, nrhs: int, algo: int = ALGO_GAUSS_JORDAN, info=N
     strideX = strideB if strideX is None else int(strideX)
     if A.dtype != B.dtype or out.dtype != B.dtype:
         raise TypeError("A, B and out must have one dtype")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batch):
-        raise ValueError("info must be an int32 tensor with at least `batch` elements")
+    _check_info(info, batch, "batch")
     with torch.cuda.device(A.device):
         _lib.check(_lib.lib().matinv_solve_batched_ex(
             algo, _torch_dtype_code(A), n, nrhs, ctypes.c_void_p(A.data_ptr()), strideA, ctypes.c_void_p(B.data_ptr()), strideB,
@@ -263,7 +280,7 @@ def solve_batched_host(As: np.ndarray, Bs: np.ndarray, n: int, nrhs: int, algo: 
 
 def solve_kernel_name(algo: int, dtype, n: int, nrhs: int, kernel: int = KERNEL_AUTO) -> str:
     """matinv_solve_kernel_name: the first kernel a solve request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_solve_kernel_name(algo, code, n, nrhs, kernel).decode()
 
 
@@ -289,8 +306,7 @@ def logdet_batched(A, n: int, algo: int = ALGO_GAUSS_JORDAN, sign=None, out=None
         raise TypeError("sign and out must have the dtype of A")
     if out.numel() < batch or sign.numel() < batch:
         raise ValueError("sign and out need at least `batch` elements")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batch):
-        raise ValueError("info must be an int32 tensor with at least `batch` elements")
+    _check_info(info, batch, "batch")
     with torch.cuda.device(A.device):
         _lib.check(_lib.lib().matinv_logdet_batched_ex(
             algo, _torch_dtype_code(A), n, ctypes.c_void_p(A.data_ptr()), stride, ctypes.c_void_p(out.data_ptr()),
@@ -326,8 +342,7 @@ def logml_batched(n, Bs, Cs, Ds, out=None, batchSize=None, info=None):
         raise TypeError("Bs, Cs, Ds and out must have one dtype")
     if Ds.numel() < batchSize * n or out.numel() < batchSize or (Cs is not None and Cs.numel() < batchSize * n):
         raise ValueError("Cs and Ds need batchSize*n elements, out batchSize")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    _check_info(info, batchSize)
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_logml_batched(
             _torch_dtype_code(Bs), n, ctypes.c_void_p(Bs.data_ptr()), ctypes.c_void_p(Cs.data_ptr()) if Cs is not None else None,
@@ -375,8 +390,7 @@ def loo_batched(n, Bs, Cs, Ds, mean=None, var=None, logpl=None, batchSize=None, 
         raise TypeError("Bs, Cs, Ds, mean, var and logpl must have one dtype")
     if any(t.numel() < batchSize * n for t in (Ds, mean, var)) or logpl.numel() < batchSize or (Cs is not None and Cs.numel() < batchSize * n):
         raise ValueError("Cs, Ds, mean and var need batchSize*n elements, logpl batchSize")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    _check_info(info, batchSize)
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_loo_batched(
             _torch_dtype_code(Bs), n, ctypes.c_void_p(Bs.data_ptr()), ctypes.c_void_p(Cs.data_ptr()) if Cs is not None else None,
@@ -408,7 +422,7 @@ def loo_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray):
 
 def loo_kernel_name(dtype, n: int) -> str:
     """matinv_loo_kernel_name: the kernel a leave-one-out request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_loo_kernel_name(code, n).decode()
 
 
@@ -449,9 +463,8 @@ def logml_grad_batched(n, Bs, Cs, Ds, dMs, grad=None, gradc=None, alpha=None, ba
         raise TypeError("Bs, Cs, Ds, dMs, grad, gradc and alpha must have one dtype")
     if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds, gradc, alpha)) or (grad is not None and grad.numel() < batchSize * nparam):
         raise ValueError("Cs, Ds, gradc and alpha need batchSize*n elements, grad batchSize*P")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_logml_grad_batched(
             _torch_dtype_code(Bs), n, nparam, p(Bs), p(Cs), p(Ds), p(dMs) if grad is not None else None, p(grad), p(gradc), p(alpha),
@@ -488,7 +501,7 @@ def logml_grad_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray, dMs, want=_GR
     if "alpha" in want:
         alpha = np.empty(batch * n, dtype=Bs.dtype)
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_logml_grad_batched_host(
         _np_dtype_code(Bs.dtype), n, nparam, p(Bs), p(Cs), p(Ds), p(dMs) if grad is not None else None, p(grad), p(gradc), p(alpha), batch,
         p(info)))
@@ -497,7 +510,7 @@ def logml_grad_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray, dMs, want=_GR
 
 def logml_grad_kernel_name(dtype, n: int) -> str:
     """matinv_logml_grad_kernel_name: the kernel a gradient request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_logml_grad_kernel_name(code, n).decode()
 
 
@@ -541,9 +554,8 @@ def loo_grad_batched(n, Bs, Cs, Ds, dMs, grad=None, gradc=None, logpl=None, batc
     if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds, gradc)) or (grad is not None and grad.numel() < batchSize * nparam) \
             or (logpl is not None and logpl.numel() < batchSize):
         raise ValueError("Cs, Ds and gradc need batchSize*n elements, grad batchSize*P, logpl batchSize")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_loo_grad_batched(
             _torch_dtype_code(Bs), n, nparam, p(Bs), p(Cs), p(Ds), p(dMs) if grad is not None else None, p(grad), p(gradc), p(logpl),
@@ -580,7 +592,7 @@ def loo_grad_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray, dMs, want=_LOO_
     if "logpl" in want:
         logpl = np.empty(batch, dtype=Bs.dtype)
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_loo_grad_batched_host(
         _np_dtype_code(Bs.dtype), n, nparam, p(Bs), p(Cs), p(Ds), p(dMs) if grad is not None else None, p(grad), p(gradc), p(logpl), batch,
         p(info)))
@@ -589,7 +601,7 @@ def loo_grad_batched_host(n, Bs: np.ndarray, Cs, Ds: np.ndarray, dMs, want=_LOO_
 
 def loo_grad_kernel_name(dtype, n: int) -> str:
     """matinv_loo_grad_kernel_name: the kernel a LOO-gradient request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_loo_grad_kernel_name(code, n).decode()
 
 
@@ -629,9 +641,8 @@ def predict_batched(n, Bs, Cs, Ds, As, Es, mean=None, var=None, batchSize=None, 
     if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds)) or \
             any(t is not None and t.numel() < batchSize * nquery for t in (Es, mean, var)):
         raise ValueError("Cs and Ds need batchSize*n elements, Es, mean and var batchSize*Q")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_predict_batched(
             _torch_dtype_code(Bs), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es), p(mean), p(var), batchSize,
@@ -661,7 +672,7 @@ def predict_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, want=_PR
     mean = np.empty(batch * nquery, dtype=Bs.dtype) if "mean" in want else None
     var = np.empty(batch * nquery, dtype=Bs.dtype) if "var" in want else None
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_predict_batched_host(
         _np_dtype_code(Bs.dtype), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es), p(mean), p(var), batch,
         p(info)))
@@ -670,7 +681,7 @@ def predict_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, want=_PR
 
 def predict_kernel_name(dtype, n: int) -> str:
     """matinv_predict_kernel_name: the kernel a prediction request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_predict_kernel_name(code, n).decode()
 
 
@@ -711,9 +722,8 @@ def predict_cov_batched(n, Bs, Cs, Ds, As, Es, mean=None, cov=None, batchSize=No
     if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds)) or (mean is not None and mean.numel() < batchSize * nquery) or \
             any(t is not None and t.numel() < batchSize * nquery * nquery for t in (Es, cov)):
         raise ValueError("Cs and Ds need batchSize*n elements, mean batchSize*Q, Es and cov batchSize*Q*Q")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_predict_cov_batched(
             _torch_dtype_code(Bs), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es) if cov is not None else None,
@@ -743,7 +753,7 @@ def predict_cov_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, want
     mean = np.empty(batch * nquery, dtype=Bs.dtype) if "mean" in want else None
     cov = np.empty(batch * nquery * nquery, dtype=Bs.dtype) if "cov" in want else None
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_predict_cov_batched_host(
         _np_dtype_code(Bs.dtype), n, nquery, p(Bs), p(Cs), p(Ds) if mean is not None else None, p(As), p(Es) if cov is not None else None,
         p(mean), p(cov), batch, p(info)))
@@ -752,7 +762,7 @@ def predict_cov_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, want
 
 def predict_cov_kernel_name(dtype, n: int) -> str:
     """matinv_predict_cov_kernel_name: the kernel a predictive-covariance request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_predict_cov_kernel_name(code, n).decode()
 
 
@@ -797,9 +807,8 @@ def colour_batched(q, Cs, Ms, Zs, Y=None, L=None, batchSize=None, info=None, wan
     if (Ms is not None and Ms.numel() < batchSize * q) or (Y is not None and Y.numel() < batchSize * nsample * q) or \
             (L is not None and L.numel() < batchSize * q * q):
         raise ValueError("Ms needs batchSize*q elements, Y batchSize*S*q, L batchSize*q*q")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Cs.device):
         _lib.check(_lib.lib().matinv_colour_batched(
             _torch_dtype_code(Cs), q, nsample, p(Cs), strideC, p(Ms) if Y is not None else None, p(Zs) if Y is not None else None, p(Y), p(L),
@@ -828,7 +837,7 @@ def colour_batched_host(q, Cs: np.ndarray, Ms, Zs, want=_COLOUR_OUTPUTS):
     Y = np.empty(batch * nsample * q, dtype=Cs.dtype) if "Y" in want else None
     L = np.empty(batch * q * q, dtype=Cs.dtype) if "L" in want else None
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_colour_batched_host(
         _np_dtype_code(Cs.dtype), q, nsample, p(Cs), q * q, p(Ms) if Y is not None else None, p(Zs) if Y is not None else None, p(Y), p(L),
         batch, p(info)))
@@ -837,7 +846,7 @@ def colour_batched_host(q, Cs: np.ndarray, Ms, Zs, want=_COLOUR_OUTPUTS):
 
 def colour_kernel_name(dtype, q: int) -> str:
     """matinv_colour_kernel_name: the kernel a colour request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_colour_kernel_name(code, q).decode()
 
 
@@ -886,9 +895,8 @@ def whiten_batched(q, Cs, Ms, Xs, W=None, maha=None, logdet=None, logpdf=None, b
         raise ValueError("Cs needs (batchSize-1)*strideC + q*q elements")
     if (Ms is not None and Ms.numel() < batchSize * q) or any(given[k] is not None and given[k].numel() < sizes[k] for k in _WHITEN_OUTPUTS):
         raise ValueError("Ms needs batchSize*q elements, W batchSize*S*q, maha and logpdf batchSize*S, logdet batchSize")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Cs.device):
         _lib.check(_lib.lib().matinv_whiten_batched(
             _torch_dtype_code(Cs), q, npoint, p(Cs), strideC, p(Ms) if points else None, p(Xs) if points else None, p(given["W"]),
@@ -918,7 +926,7 @@ def whiten_batched_host(q, Cs: np.ndarray, Ms, Xs, want=_WHITEN_OUTPUTS):
     sizes = dict(W=batch * npoint * q, maha=batch * npoint, logdet=batch, logpdf=batch * npoint)
     out = {k: np.empty(sizes[k], dtype=Cs.dtype) if k in want else None for k in _WHITEN_OUTPUTS}
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_whiten_batched_host(
         _np_dtype_code(Cs.dtype), q, npoint, p(Cs), q * q, p(Ms) if points else None, p(Xs) if points else None, p(out["W"]), p(out["maha"]),
         p(out["logdet"]), p(out["logpdf"]), batch, p(info)))
@@ -927,7 +935,7 @@ def whiten_batched_host(q, Cs: np.ndarray, Ms, Xs, want=_WHITEN_OUTPUTS):
 
 def whiten_kernel_name(dtype, q: int) -> str:
     """matinv_whiten_kernel_name: the kernel a whiten request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_whiten_kernel_name(code, q).decode()
 
 
@@ -989,9 +997,8 @@ def multi_target_batched(n, Bs, Cs, Ys, As=None, alpha=None, quad=None, logdet=N
             any(given[k] is not None and given[k].numel() < sizes[k] for k in _MULTI_TARGET_OUTPUTS):
         raise ValueError("Cs needs batchSize*n elements, alpha batchSize*D*n, quad and logml batchSize*D, logdet batchSize, "
                          "mean batchSize*D*Q")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_multi_target_batched(
             _torch_dtype_code(Bs), n, ntarget, nquery, p(Bs), p(Cs), p(Ys) if targets else None, p(As) if asked["mean"] else None,
@@ -1036,7 +1043,7 @@ def multi_target_batched_host(n, Bs: np.ndarray, Cs, Ys, As=None, want=_MULTI_TA
     sizes = dict(alpha=batch * ntarget * n, quad=batch * ntarget, logdet=batch, logml=batch * ntarget, mean=batch * ntarget * nquery)
     out = {k: np.empty(sizes[k], dtype=Bs.dtype) if k in want else None for k in _MULTI_TARGET_OUTPUTS}
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_multi_target_batched_host(
         _np_dtype_code(Bs.dtype), n, ntarget, nquery, p(Bs), p(Cs), p(Ys) if targets else None, p(As) if "mean" in want else None,
         p(out["alpha"]), p(out["quad"]), p(out["logdet"]), p(out["logml"]), p(out["mean"]), batch, p(info)))
@@ -1045,7 +1052,7 @@ def multi_target_batched_host(n, Bs: np.ndarray, Cs, Ys, As=None, want=_MULTI_TA
 
 def multi_target_kernel_name(dtype, n: int) -> str:
     """matinv_multi_target_kernel_name: the kernel a multi-target request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_multi_target_kernel_name(code, n).decode()
 
 
@@ -1100,9 +1107,8 @@ def multi_target_grad_batched(n, Bs, Cs, Ys, dMs, grad=None, gradc=None, logml=N
     if (Cs is not None and Cs.numel() < batchSize * n) or \
             any(given[k] is not None and given[k].numel() < sizes[k] for k in _MULTI_TARGET_GRAD_OUTPUTS):
         raise ValueError("Cs needs batchSize*n elements, grad batchSize*P, gradc batchSize*n, logml batchSize*D, alpha batchSize*D*n")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_multi_target_grad_batched(
             _torch_dtype_code(Bs), n, ntarget, nparam, p(Bs), p(Cs), p(Ys), p(dMs) if asked["grad"] else None, p(given["grad"]),
@@ -1142,7 +1148,7 @@ def multi_target_grad_batched_host(n, Bs: np.ndarray, Cs, Ys, dMs, want=_MULTI_T
     sizes = dict(grad=batch * nparam, gradc=batch * n, logml=batch * ntarget, alpha=batch * ntarget * n)
     out = {k: np.empty(sizes[k], dtype=Bs.dtype) if k in want else None for k in _MULTI_TARGET_GRAD_OUTPUTS}
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_multi_target_grad_batched_host(
         _np_dtype_code(Bs.dtype), n, ntarget, nparam, p(Bs), p(Cs), p(Ys), p(dMs) if "grad" in want else None, p(out["grad"]),
         p(out["gradc"]), p(out["logml"]), p(out["alpha"]), batch, p(info)))
@@ -1151,7 +1157,7 @@ def multi_target_grad_batched_host(n, Bs: np.ndarray, Cs, Ys, dMs, want=_MULTI_T
 
 def multi_target_grad_kernel_name(dtype, n: int) -> str:
     """matinv_multi_target_grad_kernel_name: the kernel a multi-target gradient request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_multi_target_grad_kernel_name(code, n).decode()
 
 
@@ -1239,11 +1245,10 @@ def trend_batched(n, Bs, Cs, Hs, Ys=None, As=None, Gs=None, Es=None, beta=None, 
     if (Cs is not None and Cs.numel() < batchSize * n) or any(given[k] is not None and given[k].numel() < sizes[k] for k in _TREND_OUTPUTS):
         raise ValueError("Cs needs batchSize*n elements, beta batchSize*D*K, covbeta batchSize*K*K, alpha batchSize*D*n, quad and logml "
                          "batchSize*D, mean batchSize*D*Q, var batchSize*Q")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
+    _check_info(info, batchSize)
     targets = any(asked[k] for k in _TREND_TARGET_OUTPUTS)
     queries = asked["mean"] or asked["var"]
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_trend_batched(
             _torch_dtype_code(Bs), n, nbasis, ntarget, nquery, p(Bs), p(Cs), p(Hs), p(Ys) if targets else None, p(As) if queries else None,
@@ -1270,7 +1275,7 @@ def trend_batched_host(n, Bs: np.ndarray, Cs, Hs, Ys=None, As=None, Gs=None, Es=
     info = np.zeros(batch, dtype=np.int32)
     targets = any(asked[k] for k in _TREND_TARGET_OUTPUTS)
     queries = asked["mean"] or asked["var"]
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_trend_batched_host(
         _np_dtype_code(Bs.dtype), n, nbasis, ntarget, nquery, p(Bs), p(Cs), p(Hs), p(Ys) if targets else None, p(As) if queries else None,
         p(Gs) if queries else None, p(Es) if asked["var"] else None, *(p(out[k]) for k in _TREND_OUTPUTS), batch, p(info)))
@@ -1279,7 +1284,7 @@ def trend_batched_host(n, Bs: np.ndarray, Cs, Hs, Ys=None, As=None, Gs=None, Es=
 
 def trend_kernel_name(dtype, n: int) -> str:
     """matinv_trend_kernel_name: the kernel a trend request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_trend_kernel_name(code, n).decode()
 
 
@@ -1323,9 +1328,8 @@ def sample_batched(n, Bs, Cs, Ds, As, Es, Zs, Y=None, mean=None, cov=None, batch
     if any(t is not None and t.numel() < batchSize * n for t in (Cs, Ds)) or (mean is not None and mean.numel() < batchSize * nquery) or \
             any(t is not None and t.numel() < batchSize * nquery * nquery for t in (Es, cov)) or Y.numel() < batchSize * nsample * nquery:
         raise ValueError("Cs and Ds need batchSize*n elements, mean batchSize*Q, Es and cov batchSize*Q*Q, Y batchSize*S*Q")
-    if info is not None and (info.dtype != torch.int32 or info.numel() < batchSize):
-        raise ValueError("info must be an int32 tensor with at least `batchSize` elements")
-    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _check_info(info, batchSize)
+    p = _tensor_ptr
     with torch.cuda.device(Bs.device):
         _lib.check(_lib.lib().matinv_sample_batched(
             _torch_dtype_code(Bs), n, nquery, nsample, p(Bs), p(Cs), p(Ds), p(As), p(Es), p(Zs), p(Y), p(mean), p(cov), batchSize, p(info),
@@ -1358,7 +1362,7 @@ def sample_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, Zs: np.nd
     mean = np.empty(batch * nquery, dtype=Bs.dtype) if "mean" in want else None
     cov = np.empty(batch * nquery * nquery, dtype=Bs.dtype) if "cov" in want else None
     info = np.zeros(batch, dtype=np.int32)
-    p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None  # noqa: E731
+    p = _array_ptr
     _lib.check(_lib.lib().matinv_sample_batched_host(
         _np_dtype_code(Bs.dtype), n, nquery, nsample, p(Bs), p(Cs), p(Ds), p(As), p(Es), p(Zs), p(Y), p(mean), p(cov), batch, p(info)))
     return Y, mean, cov, info
@@ -1366,19 +1370,19 @@ def sample_batched_host(n, Bs: np.ndarray, Cs, Ds, As: np.ndarray, Es, Zs: np.nd
 
 def logdet_kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> str:
     """matinv_logdet_kernel_name: the kernel a logdet request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_logdet_kernel_name(algo, code, n, kernel).decode()
 
 
 def gp_kernel_name(dtype, n: int, variance: bool = False) -> str:
     """matinv_gp_kernel_name: the first kernel a fused mean / variance request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_gp_kernel_name(code, n, 1 if variance else 0).decode()
 
 
 def logml_kernel_name(dtype, n: int) -> str:
     """matinv_logml_kernel_name: the first kernel a logml request launches ("" when the request would be refused)."""
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_logml_kernel_name(code, n).decode()
 
 
@@ -1402,7 +1406,7 @@ def sym_front_stats() -> dict:
 
 
 def select_kernel(algo: int, dtype, n: int) -> int:
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     k = _lib.lib().matinv_select_kernel(algo, code, n)
     if k < 0:
         _lib.check(k)
@@ -1410,5 +1414,5 @@ def select_kernel(algo: int, dtype, n: int) -> int:
 
 
 def kernel_name(algo: int, dtype, n: int, kernel: int = KERNEL_AUTO) -> str:
-    code = dtype if isinstance(dtype, int) else _np_dtype_code(dtype)
+    code = _dtype_code(dtype)
     return _lib.lib().matinv_kernel_name(algo, code, n, kernel).decode()

@@ -68,6 +68,103 @@ void staging_free(void *p)
     if (p) (void)scratch_free(p, nullptr);
 }
 
+// One buffer of a host-pointer call: the caller's pointer (null: not staged) and its element count.
+struct StagedIn {
+    const void *host;
+    size_t count;
+};
+struct StagedOut {
+    void *host;
+    size_t count;
+};
+
+// The host-pointer form of every family but gp_host and inverse_host*: allocate the non-null inputs in table order, then the non-null
+// outputs, then info; copy the inputs in; call(din, dout, dInfo) -- the device pointers in table order, null where the table's host
+// pointer is null -- which returns the rc of the family's dispatch; copy the outputs and info out when it succeeded; free everything.
+// After a first HIP error nothing further is allocated, copied or launched. What a family stages under which request is decided
+// by the pointers it puts into its tables alone.
+template <class T, size_t NI, size_t NO, class Call>
+int run_staged(const char *family, const StagedIn (&in)[NI], const StagedOut (&out)[NO], size_t batch, int *info, Call call)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    T *din[NI] = {}, *dout[NO] = {};
+    int *dInfo = nullptr;
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < NI && e == hipSuccess; ++i)
+        if (in[i].host) e = staging_alloc(reinterpret_cast<void **>(&din[i]), in[i].count * sizeof(T));
+    for (size_t i = 0; i < NO && e == hipSuccess; ++i)
+        if (out[i].host) e = staging_alloc(reinterpret_cast<void **>(&dout[i]), out[i].count * sizeof(T));
+    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
+    for (size_t i = 0; i < NI && e == hipSuccess; ++i)
+        if (din[i]) e = hipMemcpy(din[i], in[i].host, in[i].count * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess) rc = call(din, dout, dInfo);
+    for (size_t i = 0; i < NO && e == hipSuccess && rc == MATINV_OK; ++i)
+        if (dout[i]) e = hipMemcpy(out[i].host, dout[i], out[i].count * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
+    for (T *p : din) staging_free(p);
+    for (T *p : dout) staging_free(p);
+    staging_free(dInfo);
+    if (rc != MATINV_OK) return rc;
+    if (e != hipSuccess) return fail_hip(e, (std::string(family) + " host<->device").c_str());
+    return MATINV_OK;
+}
+
+// ---- the argument checks every family shares: one message each. A family's *_check_args reads: check_head, `if (batch == 0) return
+// MATINV_OK;`, its own lines, check_tail, its own count limits. `name` is what the family calls its matrix order: "n" or "q". ---------
+int check_order(const char *name, int n)
+{
+    if (n < 1) return fail(MATINV_ERR_ARG, "%s must be >= 1 (got %d)", name, n);
+    return MATINV_OK;
+}
+
+int check_dtype(int dtype)
+{
+    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return MATINV_OK;
+}
+
+// checked even for an empty batch
+int check_head(const char *name, int n, int dtype)
+{
+    const int rc = check_order(name, n);
+    return rc ? rc : check_dtype(dtype);
+}
+
+int check_batch(size_t batch)
+{
+    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
+    return MATINV_OK;
+}
+
+// after the family's pointer and output checks: the grid limit, then the largest order any kernel family serves
+int check_tail(const char *name, int n, size_t batch)
+{
+    const int rc = check_batch(batch);
+    if (rc) return rc;
+    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "%s=%d exceeds every kernel family built in (limit 1024)", name, n);
+    return MATINV_OK;
+}
+
+// the per-call limit of a count (nquery, ntarget, nsample, npoint, nparam); `things` is what it counts
+int check_count(const char *name, int count, const char *things)
+{
+    if (count > 1024) return fail(MATINV_ERR_UNSUPPORTED, "%s=%d exceeds the limit of 1024 %s per call", name, count, things);
+    return MATINV_OK;
+}
+
+// The one dtype switch of the C ABI: f is a generic lambda, called with a value of the element type.
+template <class F>
+int by_dtype(int dtype, F f)
+{
+    if (dtype == MATINV_F64) return f(double());
+    if (dtype == MATINV_F32) return f(float());
+    return check_dtype(dtype);
+}
+
+// The guard of the GP families' matinv_*_kernel_name functions: they answer "" for an order or a dtype that no launch accepts.
+bool has_kernel_name(int dtype, int n) { return n >= 1 && n <= 1024 && (dtype == MATINV_F64 || dtype == MATINV_F32); }
+
 template <class T>
 int select_auto(int algo, int n)
 {
@@ -110,12 +207,12 @@ template <class T>
 int inverse_dispatch(int algo, int n, BatchRef<const T> A, BatchRef<T> X, size_t batch, int *dInfo, hipStream_t stream,
                      int kernel, int chol_phases = 7)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (int rc = check_order("n", n)) return rc;
     if (algo != MATINV_ALGO_GAUSS_JORDAN && algo != MATINV_ALGO_CHOLESKY)
         return fail(MATINV_ERR_ARG, "unknown algorithm %d", algo);
     if (batch == 0) return MATINV_OK;
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    int rc = check_device();
+    int rc = check_batch(batch);
+    if (rc == MATINV_OK) rc = check_device();
     if (rc) return rc;
     if (kernel == MATINV_KERNEL_AUTO) {
         // the Cholesky sub-phase entry points (factor only, ...) exist in the LDS family only
@@ -187,7 +284,7 @@ template <class T>
 int inverse_strided(int algo, int n, const void *dA, size_t strideA, void *dAinv, size_t strideInv, size_t batch,
                     int *dInfo, void *stream, int kernel)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (int rc = check_order("n", n)) return rc;
     if (batch && (!dA || !dAinv)) return fail(MATINV_ERR_ARG, "null device pointer");
     if (batch > 1 && (strideA < (size_t)n * n || strideInv < (size_t)n * n))
         return fail(MATINV_ERR_ARG, "stride smaller than n*n");
@@ -480,7 +577,7 @@ template <class T>
 int inverse_table(int algo, int n, T *const *hostIn, T *const *hostOut, size_t batch, int chol_phases = 7,
                   int kernel = MATINV_KERNEL_AUTO)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (int rc = check_order("n", n)) return rc;
     if (batch == 0) return MATINV_OK;
     if (!hostIn || !hostOut) return fail(MATINV_ERR_ARG, "null pointer table");
     auto uniform = [&](T *const *tab, size_t &stride) {
@@ -543,19 +640,17 @@ int solve_route(int algo, int n, int nrhs, int kernel, int &family)
 int solve_check_args(int algo, int dtype, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB, void *dX,
                      size_t strideX, size_t batch, int kernel)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (int rc = check_order("n", n)) return rc;
     if (nrhs < 1) return fail(MATINV_ERR_ARG, "nrhs must be >= 1 (got %d)", nrhs);
     if (algo != MATINV_ALGO_GAUSS_JORDAN && algo != MATINV_ALGO_CHOLESKY) return fail(MATINV_ERR_ARG, "unknown algorithm %d", algo);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_dtype(dtype)) return rc;
     if (kernel < MATINV_KERNEL_AUTO || kernel > MATINV_KERNEL_TILEP) return fail(MATINV_ERR_ARG, "unknown kernel family %d", kernel);
     if (batch == 0) return MATINV_OK;
     if (!dA || !dB || !dX) return fail(MATINV_ERR_ARG, "null device pointer");
     const size_t nb = (size_t)n * (size_t)nrhs;
     if (batch > 1 && (strideA < (size_t)n * n || strideB < nb || strideX < nb))
         return fail(MATINV_ERR_ARG, "stride too small (strideA >= n*n, strideB and strideX >= n*nrhs)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    return MATINV_OK;
+    return check_tail("n", n, batch);
 }
 
 template <class T>
@@ -606,28 +701,12 @@ template <class T>
 int solve_host(int algo, int n, int nrhs, const void *hA, const void *hB, void *hX, size_t batch, int *info)
 {
     const size_t ea = (size_t)n * n * batch, eb = (size_t)n * nrhs * batch;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dA = nullptr, *dB = nullptr, *dX = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dA), ea * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dB), eb * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dX), eb * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dA, hA, ea * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dB, hB, eb * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = solve_strided<T>(algo, n, nrhs, dA, (size_t)n * n, dB, (size_t)n * nrhs, dX, (size_t)n * nrhs, batch, dInfo, nullptr,
-                              MATINV_KERNEL_AUTO);
-    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hX, dX, eb * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dA);
-    staging_free(dB);
-    staging_free(dX);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "solve host<->device");
-    return MATINV_OK;
+    const StagedIn in[] = {{hA, ea}, {hB, eb}};
+    const StagedOut out[] = {{hX, eb}};
+    return run_staged<T>("solve", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return solve_strided<T>(algo, n, nrhs, i[0], (size_t)n * n, i[1], (size_t)n * nrhs, o[0], (size_t)n * nrhs, batch, dInfo, nullptr,
+                                MATINV_KERNEL_AUTO);
+    });
 }
 
 // Which kernel a fused mean / variance request takes (the name function and the launcher both ask here):
@@ -654,11 +733,11 @@ template <class T>
 int gp_dispatch(int n, const void *a, const void *B, const void *c, const void *d, const void *e_, void *out,
                 size_t batch, int *dInfo, void *stream, bool variance)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (int rc = check_order("n", n)) return rc;
     if (batch == 0) return MATINV_OK;
     if (!a || !B || !c || !out || (variance ? !e_ : !d)) return fail(MATINV_ERR_ARG, "null device pointer");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    int rc = check_device();
+    int rc = check_batch(batch);
+    if (rc == MATINV_OK) rc = check_device();
     if (rc) return rc;
     const int route = gp_route<T>(n);
     if (route < 0) return route;
@@ -758,16 +837,14 @@ int logdet_route(int algo, int n, int kernel)
 
 int logdet_check_args(int algo, int dtype, int n, const void *dA, size_t strideA, const void *dLogAbsDet, size_t batch, int kernel)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (int rc = check_order("n", n)) return rc;
     if (algo != MATINV_ALGO_GAUSS_JORDAN && algo != MATINV_ALGO_CHOLESKY) return fail(MATINV_ERR_ARG, "unknown algorithm %d", algo);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_dtype(dtype)) return rc;
     if (kernel < MATINV_KERNEL_AUTO || kernel > MATINV_KERNEL_TILEP) return fail(MATINV_ERR_ARG, "unknown kernel family %d", kernel);
     if (batch == 0) return MATINV_OK;
     if (!dA || !dLogAbsDet) return fail(MATINV_ERR_ARG, "null device pointer");
     if (batch > 1 && strideA < (size_t)n * n) return fail(MATINV_ERR_ARG, "stride too small (strideA >= n*n)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    return MATINV_OK;
+    return check_tail("n", n, batch);
 }
 
 template <class T>
@@ -791,37 +868,19 @@ int logdet_strided(int algo, int n, const void *dA, size_t strideA, void *dLogAb
 template <class T>
 int logdet_host(int algo, int n, const void *hA, void *hLogAbsDet, void *hSign, size_t batch, int *info)
 {
-    const size_t ea = (size_t)n * n * batch;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dA = nullptr, *dOut = nullptr;  // dOut: logabsdet, then sign
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dA), ea * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dOut), 2 * batch * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dA, hA, ea * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = logdet_strided<T>(algo, n, dA, (size_t)n * n, dOut, hSign ? dOut + batch : nullptr, batch, dInfo, nullptr, MATINV_KERNEL_AUTO);
-    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hLogAbsDet, dOut, batch * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hSign) e = hipMemcpy(hSign, dOut + batch, batch * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dA);
-    staging_free(dOut);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "logdet host<->device");
-    return MATINV_OK;
+    const StagedIn in[] = {{hA, (size_t)n * n * batch}};
+    const StagedOut out[] = {{hLogAbsDet, batch}, {hSign, batch}};
+    return run_staged<T>("logdet", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return logdet_strided<T>(algo, n, i[0], (size_t)n * n, o[0], o[1], batch, dInfo, nullptr, MATINV_KERNEL_AUTO);
+    });
 }
 
 int logml_check_args(int dtype, int n, const void *dBs, const void *dDs, const void *dLogml, size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (!dBs || !dDs || !dLogml) return fail(MATINV_ERR_ARG, "null device pointer");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    return MATINV_OK;
+    return check_tail("n", n, batch);
 }
 
 // n <= 96: the bordered tile kernel. Beyond: the variance pipeline with a = d and e = 0 puts -d^T M^-1 d into scratch, the global
@@ -866,39 +925,21 @@ template <class T>
 int logml_host(int n, const void *hBs, const void *hCs, const void *hDs, void *hLogml, size_t batch, int *info)
 {
     const size_t vec = (size_t)n * batch, mat = vec * n;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dOut = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dOut), batch * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = logml_dispatch<T>(n, dB, dC, dD, dOut, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hLogml, dOut, batch * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dOut);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "logml host<->device");
-    return MATINV_OK;
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hDs, vec}};
+    const StagedOut out[] = {{hLogml, batch}};
+    return run_staged<T>("logml", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return logml_dispatch<T>(n, i[0], i[1], i[2], o[0], batch, dInfo, nullptr);
+    });
 }
 
 // ---- batched leave-one-out cross-validation of a GP (matinv_loo_batched) ---------------------------------------------------------------
 int loo_check_args(int dtype, int n, const void *dBs, const void *dDs, const void *dMean, const void *dVar, const void *dLogPL, size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (!dBs || !dDs) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!dMean && !dVar && !dLogPL) return fail(MATINV_ERR_ARG, "no output requested (mean, var and logpl are all null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    return MATINV_OK;
+    return check_tail("n", n, batch);
 }
 
 // n <= 96: the LOO form of the one-wavefront SPD sweep. Beyond, to n = 1024: the LOO form of the global-memory Cholesky kernel.
@@ -920,47 +961,25 @@ template <class T>
 int loo_host(int n, const void *hBs, const void *hCs, const void *hDs, void *hMean, void *hVar, void *hLogPL, size_t batch, int *info)
 {
     const size_t vec = (size_t)n * batch, mat = vec * n;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dMean = nullptr, *dVar = nullptr, *dLogPL = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMean), vec * sizeof(T));
-    if (e == hipSuccess && hVar) e = staging_alloc(reinterpret_cast<void **>(&dVar), vec * sizeof(T));
-    if (e == hipSuccess && hLogPL) e = staging_alloc(reinterpret_cast<void **>(&dLogPL), batch * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = loo_dispatch<T>(n, dB, dC, dD, dMean, dVar, dLogPL, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMean, vec * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hVar) e = hipMemcpy(hVar, dVar, vec * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hLogPL) e = hipMemcpy(hLogPL, dLogPL, batch * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dMean), staging_free(dVar), staging_free(dLogPL);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "loo host<->device");
-    return MATINV_OK;
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hDs, vec}};
+    const StagedOut out[] = {{hMean, vec}, {hVar, vec}, {hLogPL, batch}};
+    return run_staged<T>("loo", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return loo_dispatch<T>(n, i[0], i[1], i[2], o[0], o[1], o[2], batch, dInfo, nullptr);
+    });
 }
 
 // ---- gradients of the batched GP log marginal likelihood (matinv_logml_grad_batched) -------------------------------------------------
 int logml_grad_check_args(int dtype, int n, int nparam, const void *dBs, const void *dDs, const void *dDMs, const void *dGrad,
                           const void *dGradC, const void *dAlpha, size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (nparam < 0) return fail(MATINV_ERR_ARG, "nparam must be >= 0 (got %d)", nparam);
     if (!dBs || !dDs) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!dGrad && !dGradC && !dAlpha) return fail(MATINV_ERR_ARG, "no output requested (grad, gradc and alpha are all null)");
     if (dGrad && nparam < 1) return fail(MATINV_ERR_ARG, "grad requested with nparam = 0");
     if (dGrad && !dDMs) return fail(MATINV_ERR_ARG, "grad requested without derivative matrices (dDMs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    return MATINV_OK;
+    return check_tail("n", n, batch);
 }
 
 // n <= 96: the gradient form of the one-wavefront SPD sweep. Beyond, to n = 1024: the gradient form of the global-memory Cholesky kernel.
@@ -985,49 +1004,26 @@ int logml_grad_host(int n, int nparam, const void *hBs, const void *hCs, const v
                     void *hAlpha, size_t batch, int *info)
 {
     const size_t vec = (size_t)n * batch, mat = vec * n, par = batch * (size_t)nparam;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dDM = nullptr, *dGrad = nullptr, *dGradC = nullptr, *dAlpha = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
-    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dDM), par * (size_t)n * n * sizeof(T));
-    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dGrad), par * sizeof(T));
-    if (e == hipSuccess && hGradC) e = staging_alloc(reinterpret_cast<void **>(&dGradC), vec * sizeof(T));
-    if (e == hipSuccess && hAlpha) e = staging_alloc(reinterpret_cast<void **>(&dAlpha), vec * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hGrad) e = hipMemcpy(dDM, hDMs, par * (size_t)n * n * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = logml_grad_dispatch<T>(n, nparam, dB, dC, dD, dDM, dGrad, dGradC, dAlpha, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hGrad) e = hipMemcpy(hGrad, dGrad, par * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hGradC) e = hipMemcpy(hGradC, dGradC, vec * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hAlpha) e = hipMemcpy(hAlpha, dAlpha, vec * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dDM), staging_free(dGrad), staging_free(dGradC), staging_free(dAlpha);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "logml_grad host<->device");
-    return MATINV_OK;
+    // the derivative matrices are read for grad only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hDs, vec}, {hGrad ? hDMs : nullptr, par * (size_t)n * n}};
+    const StagedOut out[] = {{hGrad, par}, {hGradC, vec}, {hAlpha, vec}};
+    return run_staged<T>("logml_grad", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return logml_grad_dispatch<T>(n, nparam, i[0], i[1], i[2], i[3], o[0], o[1], o[2], batch, dInfo, nullptr);
+    });
 }
 
 // ---- gradients of the batched GP leave-one-out log pseudo-likelihood (matinv_loo_grad_batched) -----------------------------------------
 int loo_grad_check_args(int dtype, int n, int nparam, const void *dBs, const void *dDs, const void *dDMs, const void *dGrad,
                         const void *dGradC, const void *dLogPL, size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (nparam < 0) return fail(MATINV_ERR_ARG, "nparam must be >= 0 (got %d)", nparam);
     if (!dBs || !dDs) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!dGrad && !dGradC && !dLogPL) return fail(MATINV_ERR_ARG, "no output requested (grad, gradc and logpl are all null)");
     if (dGrad && nparam < 1) return fail(MATINV_ERR_ARG, "grad requested with nparam = 0");
     if (dGrad && !dDMs) return fail(MATINV_ERR_ARG, "grad requested without derivative matrices (dDMs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    return MATINV_OK;
+    return check_tail("n", n, batch);
 }
 
 // n <= 96: the LOO-gradient form of the one-wavefront SPD sweep. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
@@ -1052,48 +1048,25 @@ int loo_grad_host(int n, int nparam, const void *hBs, const void *hCs, const voi
                   void *hLogPL, size_t batch, int *info)
 {
     const size_t vec = (size_t)n * batch, mat = vec * n, par = batch * (size_t)nparam;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dDM = nullptr, *dGrad = nullptr, *dGradC = nullptr, *dLogPL = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
-    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dDM), par * (size_t)n * n * sizeof(T));
-    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dGrad), par * sizeof(T));
-    if (e == hipSuccess && hGradC) e = staging_alloc(reinterpret_cast<void **>(&dGradC), vec * sizeof(T));
-    if (e == hipSuccess && hLogPL) e = staging_alloc(reinterpret_cast<void **>(&dLogPL), batch * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hGrad) e = hipMemcpy(dDM, hDMs, par * (size_t)n * n * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = loo_grad_dispatch<T>(n, nparam, dB, dC, dD, dDM, dGrad, dGradC, dLogPL, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hGrad) e = hipMemcpy(hGrad, dGrad, par * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hGradC) e = hipMemcpy(hGradC, dGradC, vec * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hLogPL) e = hipMemcpy(hLogPL, dLogPL, batch * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dDM), staging_free(dGrad), staging_free(dGradC), staging_free(dLogPL);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "loo_grad host<->device");
-    return MATINV_OK;
+    // the derivative matrices are read for grad only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hDs, vec}, {hGrad ? hDMs : nullptr, par * (size_t)n * n}};
+    const StagedOut out[] = {{hGrad, par}, {hGradC, vec}, {hLogPL, batch}};
+    return run_staged<T>("loo_grad", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return loo_grad_dispatch<T>(n, nparam, i[0], i[1], i[2], i[3], o[0], o[1], o[2], batch, dInfo, nullptr);
+    });
 }
 
 // ---- batched GP prediction at many query points per matrix (matinv_predict_batched) ---------------------------------------------------
 int predict_check_args(int dtype, int n, int nquery, const void *dBs, const void *dDs, const void *dAs, const void *dMean, const void *dVar,
                        size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 (got %d)", nquery);
     if (!dBs || !dAs) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!dMean && !dVar) return fail(MATINV_ERR_ARG, "no output requested (mean and var are both null)");
     if (dMean && !dDs) return fail(MATINV_ERR_ARG, "mean requested without the observations (dDs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    return MATINV_OK;
+    return check_tail("n", n, batch);
 }
 
 // n <= 96: the prediction form of the one-wavefront SPD sweep. Beyond, to n = 1024: the prediction form of the global-memory Cholesky kernel.
@@ -1117,49 +1090,26 @@ int predict_host(int n, int nquery, const void *hBs, const void *hCs, const void
                  void *hVar, size_t batch, int *info)
 {
     const size_t vec = (size_t)n * batch, mat = vec * n, qs = batch * (size_t)nquery;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dA = nullptr, *dE = nullptr, *dMean = nullptr, *dVar = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dA), qs * (size_t)n * sizeof(T));
-    if (e == hipSuccess && hEs && hVar) e = staging_alloc(reinterpret_cast<void **>(&dE), qs * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMean), qs * sizeof(T));
-    if (e == hipSuccess && hVar) e = staging_alloc(reinterpret_cast<void **>(&dVar), qs * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hMean) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, hAs, qs * (size_t)n * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dE) e = hipMemcpy(dE, hEs, qs * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = predict_dispatch<T>(n, nquery, dB, dC, dD, dA, dE, dMean, dVar, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMean, qs * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hVar) e = hipMemcpy(hVar, dVar, qs * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dA), staging_free(dE), staging_free(dMean), staging_free(dVar);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "predict host<->device");
-    return MATINV_OK;
+    // the observations are read for mean only, the prior variances for var only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hMean ? hDs : nullptr, vec}, {hAs, qs * (size_t)n}, {hVar ? hEs : nullptr, qs}};
+    const StagedOut out[] = {{hMean, qs}, {hVar, qs}};
+    return run_staged<T>("predict", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return predict_dispatch<T>(n, nquery, i[0], i[1], i[2], i[3], i[4], o[0], o[1], batch, dInfo, nullptr);
+    });
 }
 
 // ---- batched joint predictive covariance between the query points of a matrix (matinv_predict_cov_batched) ----------------------------
 int predict_cov_check_args(int dtype, int n, int nquery, const void *dBs, const void *dDs, const void *dAs, const void *dMean,
                            const void *dCov, size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 (got %d)", nquery);
     if (!dBs || !dAs) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!dMean && !dCov) return fail(MATINV_ERR_ARG, "no output requested (mean and cov are both null)");
     if (dMean && !dDs) return fail(MATINV_ERR_ARG, "mean requested without the observations (dDs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    if (nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
-    return MATINV_OK;
+    if (int rc = check_tail("n", n, batch)) return rc;
+    return check_count("nquery", nquery, "query points");
 }
 
 // n <= 96: the covariance form of the one-wavefront SPD sweep. Beyond, to n = 1024: the covariance form of the global-memory Cholesky kernel.
@@ -1184,50 +1134,28 @@ int predict_cov_host(int n, int nquery, const void *hBs, const void *hCs, const 
                      void *hCov, size_t batch, int *info)
 {
     const size_t vec = (size_t)n * batch, mat = vec * n, qs = batch * (size_t)nquery, qq = qs * (size_t)nquery;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dA = nullptr, *dE = nullptr, *dMean = nullptr, *dCov = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dA), qs * (size_t)n * sizeof(T));
-    if (e == hipSuccess && hEs && hCov) e = staging_alloc(reinterpret_cast<void **>(&dE), qq * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMean), qs * sizeof(T));
-    if (e == hipSuccess && hCov) e = staging_alloc(reinterpret_cast<void **>(&dCov), qq * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hMean) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, hAs, qs * (size_t)n * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dE) e = hipMemcpy(dE, hEs, qq * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = predict_cov_dispatch<T>(n, nquery, dB, dC, dD, dA, dE, dMean, dCov, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMean, qs * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hCov) e = hipMemcpy(hCov, dCov, qq * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dA), staging_free(dE), staging_free(dMean), staging_free(dCov);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "predict_cov host<->device");
-    return MATINV_OK;
+    // the observations are read for mean only, the prior covariances for cov only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hMean ? hDs : nullptr, vec}, {hAs, qs * (size_t)n}, {hCov ? hEs : nullptr, qq}};
+    const StagedOut out[] = {{hMean, qs}, {hCov, qq}};
+    return run_staged<T>("predict_cov", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return predict_cov_dispatch<T>(n, nquery, i[0], i[1], i[2], i[3], i[4], o[0], o[1], batch, dInfo, nullptr);
+    });
 }
 
 // ---- batched Cholesky factor and coloured samples Y = m + chol(C) Z (matinv_colour_batched) ---------------------------------------------
 int colour_check_args(int dtype, int q, int nsample, const void *dC, size_t strideC, const void *dZ, const void *dY, const void *dL,
                       size_t batch)
 {
-    if (q < 1) return fail(MATINV_ERR_ARG, "q must be >= 1 (got %d)", q);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("q", q, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (!dC) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!dY && !dL) return fail(MATINV_ERR_ARG, "no output requested (Y and L are both null)");
     if (dY && !dZ) return fail(MATINV_ERR_ARG, "Y requested without the samples (dZ is null)");
     if (dY && nsample < 1) return fail(MATINV_ERR_ARG, "nsample must be >= 1 with Y (got %d)", nsample);
     if (strideC < (size_t)q * q) return fail(MATINV_ERR_ARG, "strideC %zu is smaller than q*q", strideC);
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (q > 1024) return fail(MATINV_ERR_UNSUPPORTED, "q=%d exceeds every kernel family built in (limit 1024)", q);
-    if (dY && nsample > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nsample=%d exceeds the limit of 1024 samples per call", nsample);
-    return MATINV_OK;
+    int rc = check_tail("q", q, batch);
+    if (rc == MATINV_OK && dY) rc = check_count("nsample", nsample, "samples");
+    return rc;
 }
 
 // q <= 96: the colour form of the one-wavefront SPD sweep. Beyond, to q = 1024: the colour form of the global-memory Cholesky kernel.
@@ -1251,27 +1179,12 @@ int colour_host(int q, int nsample, const void *hC, size_t strideC, const void *
                 int *info)
 {
     const size_t vec = (size_t)q * batch, mat = vec * q, ys = hY ? vec * (size_t)nsample : 0, cs = (batch - 1) * strideC + (size_t)q * q;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dC = nullptr, *dM = nullptr, *dZ = nullptr, *dY = nullptr, *dL = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dC), cs * sizeof(T));
-    if (e == hipSuccess && hM && hY) e = staging_alloc(reinterpret_cast<void **>(&dM), vec * sizeof(T));
-    if (e == hipSuccess && hY) e = staging_alloc(reinterpret_cast<void **>(&dZ), ys * sizeof(T));
-    if (e == hipSuccess && hY) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
-    if (e == hipSuccess && hL) e = staging_alloc(reinterpret_cast<void **>(&dL), mat * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dC, hC, cs * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dM) e = hipMemcpy(dM, hM, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dZ) e = hipMemcpy(dZ, hZ, ys * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = colour_dispatch<T>(q, nsample, dC, strideC, dM, dZ, dY, dL, batch, dInfo, 0, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hY) e = hipMemcpy(hY, dY, ys * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hL) e = hipMemcpy(hL, dL, mat * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dC), staging_free(dM), staging_free(dZ), staging_free(dY), staging_free(dL), staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "colour host<->device");
-    return MATINV_OK;
+    // the mean and the samples are read for Y only
+    const StagedIn in[] = {{hC, cs}, {hY ? hM : nullptr, vec}, {hY ? hZ : nullptr, ys}};
+    const StagedOut out[] = {{hY, ys}, {hL, mat}};
+    return run_staged<T>("colour", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return colour_dispatch<T>(q, nsample, i[0], strideC, i[1], i[2], o[0], o[1], batch, dInfo, 0, nullptr);
+    });
 }
 
 // ---- batched whitening W = chol(C)^-1 (X - m), Mahalanobis distances and Gaussian log-density (matinv_whiten_batched) ------------------
@@ -1280,18 +1193,16 @@ int whiten_check_args(int dtype, int q, int npoint, const void *dC, size_t strid
                       const void *dLogdet, const void *dLogpdf, size_t batch)
 {
     const bool points = dW || dMaha || dLogpdf;
-    if (q < 1) return fail(MATINV_ERR_ARG, "q must be >= 1 (got %d)", q);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("q", q, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (!dC) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!points && !dLogdet) return fail(MATINV_ERR_ARG, "no output requested (W, maha, logdet and logpdf are all null)");
     if (points && !dX) return fail(MATINV_ERR_ARG, "W, maha or logpdf requested without the points (dX is null)");
     if (points && npoint < 1) return fail(MATINV_ERR_ARG, "npoint must be >= 1 with W, maha or logpdf (got %d)", npoint);
     if (strideC < (size_t)q * q) return fail(MATINV_ERR_ARG, "strideC %zu is smaller than q*q", strideC);
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (q > 1024) return fail(MATINV_ERR_UNSUPPORTED, "q=%d exceeds every kernel family built in (limit 1024)", q);
-    if (points && npoint > 1024) return fail(MATINV_ERR_UNSUPPORTED, "npoint=%d exceeds the limit of 1024 points per call", npoint);
-    return MATINV_OK;
+    int rc = check_tail("q", q, batch);
+    if (rc == MATINV_OK && points) rc = check_count("npoint", npoint, "points");
+    return rc;
 }
 
 // q <= 96: the whiten form of the one-wavefront SPD sweep. Beyond, to q = 1024: the whiten form of the global-memory Cholesky kernel.
@@ -1316,32 +1227,12 @@ int whiten_host(int q, int npoint, const void *hC, size_t strideC, const void *h
     const bool points = hW || hMaha || hLogpdf;
     const size_t vec = (size_t)q * batch, ps = points ? batch * (size_t)npoint : 0, xs = vec * (points ? (size_t)npoint : 0);
     const size_t cs = (batch - 1) * strideC + (size_t)q * q;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dC = nullptr, *dM = nullptr, *dX = nullptr, *dW = nullptr, *dMh = nullptr, *dLd = nullptr, *dLp = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dC), cs * sizeof(T));
-    if (e == hipSuccess && hM && points) e = staging_alloc(reinterpret_cast<void **>(&dM), vec * sizeof(T));
-    if (e == hipSuccess && points) e = staging_alloc(reinterpret_cast<void **>(&dX), xs * sizeof(T));
-    if (e == hipSuccess && hW) e = staging_alloc(reinterpret_cast<void **>(&dW), xs * sizeof(T));
-    if (e == hipSuccess && hMaha) e = staging_alloc(reinterpret_cast<void **>(&dMh), ps * sizeof(T));
-    if (e == hipSuccess && hLogdet) e = staging_alloc(reinterpret_cast<void **>(&dLd), batch * sizeof(T));
-    if (e == hipSuccess && hLogpdf) e = staging_alloc(reinterpret_cast<void **>(&dLp), ps * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dC, hC, cs * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dM) e = hipMemcpy(dM, hM, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dX) e = hipMemcpy(dX, hX, xs * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = whiten_dispatch<T>(q, npoint, dC, strideC, dM, dX, dW, dMh, dLd, dLp, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hW) e = hipMemcpy(hW, dW, xs * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hMaha) e = hipMemcpy(hMaha, dMh, ps * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hLogdet) e = hipMemcpy(hLogdet, dLd, batch * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hLogpdf) e = hipMemcpy(hLogpdf, dLp, ps * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dC), staging_free(dM), staging_free(dX), staging_free(dW), staging_free(dMh), staging_free(dLd), staging_free(dLp);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "whiten host<->device");
-    return MATINV_OK;
+    // the mean and the points are read for the per-point outputs only
+    const StagedIn in[] = {{hC, cs}, {points ? hM : nullptr, vec}, {points ? hX : nullptr, xs}};
+    const StagedOut out[] = {{hW, xs}, {hMaha, ps}, {hLogdet, batch}, {hLogpdf, ps}};
+    return run_staged<T>("whiten", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return whiten_dispatch<T>(q, npoint, i[0], strideC, i[1], i[2], o[0], o[1], o[2], o[3], batch, dInfo, nullptr);
+    });
 }
 
 // ---- batched multi-output GP solves: many target vectors per covariance matrix (matinv_multi_target_batched) ---------------------------
@@ -1350,8 +1241,7 @@ int multi_target_check_args(int dtype, int n, int ntarget, int nquery, const voi
                             const void *dQuad, const void *dLogdet, const void *dLogml, const void *dMean, size_t batch)
 {
     const bool targets = dAlpha || dQuad || dLogml || dMean;
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (targets && ntarget < 1) return fail(MATINV_ERR_ARG, "ntarget must be >= 1 with alpha, quad, logml or mean (got %d)", ntarget);
     if (dMean && nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 with mean (got %d)", nquery);
@@ -1359,11 +1249,10 @@ int multi_target_check_args(int dtype, int n, int ntarget, int nquery, const voi
     if (!targets && !dLogdet) return fail(MATINV_ERR_ARG, "no output requested (alpha, quad, logdet, logml and mean are all null)");
     if (targets && !dYs) return fail(MATINV_ERR_ARG, "alpha, quad, logml or mean requested without the targets (dYs is null)");
     if (dMean && !dAs) return fail(MATINV_ERR_ARG, "mean requested without the query vectors (dAs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    if (targets && ntarget > 1024) return fail(MATINV_ERR_UNSUPPORTED, "ntarget=%d exceeds the limit of 1024 targets per call", ntarget);
-    if (dMean && nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
-    return MATINV_OK;
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK && targets) rc = check_count("ntarget", ntarget, "targets");
+    if (rc == MATINV_OK && dMean) rc = check_count("nquery", nquery, "query points");
+    return rc;
 }
 
 // n <= 96: the multi-target form of the one-wavefront SPD sweep. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
@@ -1391,37 +1280,12 @@ int multi_target_host(int n, int ntarget, int nquery, const void *hBs, const voi
     const bool targets = hAlpha || hQuad || hLogml || hMean;
     const size_t vec = (size_t)n * batch, mat = vec * n, ts = targets ? batch * (size_t)ntarget : 0, ys = ts * n;
     const size_t qs = hMean ? batch * (size_t)nquery : 0, ms = hMean ? ts * (size_t)nquery : 0;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dY = nullptr, *dA = nullptr, *dAl = nullptr, *dQd = nullptr, *dLd = nullptr, *dLm = nullptr;
-    T *dMn = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess && targets) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dA), qs * (size_t)n * sizeof(T));
-    if (e == hipSuccess && hAlpha) e = staging_alloc(reinterpret_cast<void **>(&dAl), ys * sizeof(T));
-    if (e == hipSuccess && hQuad) e = staging_alloc(reinterpret_cast<void **>(&dQd), ts * sizeof(T));
-    if (e == hipSuccess && hLogdet) e = staging_alloc(reinterpret_cast<void **>(&dLd), batch * sizeof(T));
-    if (e == hipSuccess && hLogml) e = staging_alloc(reinterpret_cast<void **>(&dLm), ts * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMn), ms * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dY) e = hipMemcpy(dY, hYs, ys * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dA) e = hipMemcpy(dA, hAs, qs * (size_t)n * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = multi_target_dispatch<T>(n, ntarget, nquery, dB, dC, dY, dA, dAl, dQd, dLd, dLm, dMn, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hAlpha) e = hipMemcpy(hAlpha, dAl, ys * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hQuad) e = hipMemcpy(hQuad, dQd, ts * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hLogdet) e = hipMemcpy(hLogdet, dLd, batch * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hLogml) e = hipMemcpy(hLogml, dLm, ts * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMn, ms * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dY), staging_free(dA), staging_free(dAl), staging_free(dQd), staging_free(dLd);
-    staging_free(dLm), staging_free(dMn), staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "multi_target host<->device");
-    return MATINV_OK;
+    // the targets are read for every output but logdet, the query vectors for mean only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {targets ? hYs : nullptr, ys}, {hMean ? hAs : nullptr, qs * (size_t)n}};
+    const StagedOut out[] = {{hAlpha, ys}, {hQuad, ts}, {hLogdet, batch}, {hLogml, ts}, {hMean, ms}};
+    return run_staged<T>("multi_target", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return multi_target_dispatch<T>(n, ntarget, nquery, i[0], i[1], i[2], i[3], o[0], o[1], o[2], o[3], o[4], batch, dInfo, nullptr);
+    });
 }
 
 // ---- gradients of the multi-output GP log marginal likelihood (matinv_multi_target_grad_batched) ---------------------------------------
@@ -1429,8 +1293,7 @@ int multi_target_host(int n, int ntarget, int nquery, const void *hBs, const voi
 int multi_target_grad_check_args(int dtype, int n, int ntarget, int nparam, const void *dBs, const void *dYs, const void *dDMs,
                                  const void *dGrad, const void *dGradC, const void *dLogml, const void *dAlpha, size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (ntarget < 1) return fail(MATINV_ERR_ARG, "ntarget must be >= 1 (got %d)", ntarget);
     if (nparam < 0 || (dGrad && nparam < 1)) return fail(MATINV_ERR_ARG, "nparam must be >= 1 with grad, >= 0 without (got %d)", nparam);
@@ -1438,11 +1301,10 @@ int multi_target_grad_check_args(int dtype, int n, int ntarget, int nparam, cons
     if (!dGrad && !dGradC && !dLogml && !dAlpha) return fail(MATINV_ERR_ARG, "no output requested (grad, gradc, logml and alpha are all null)");
     if (!dYs) return fail(MATINV_ERR_ARG, "the targets are needed for every output (dYs is null)");
     if (dGrad && !dDMs) return fail(MATINV_ERR_ARG, "grad requested without derivative matrices (dDMs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    if (ntarget > 1024) return fail(MATINV_ERR_UNSUPPORTED, "ntarget=%d exceeds the limit of 1024 targets per call", ntarget);
-    if (dGrad && nparam > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nparam=%d exceeds the limit of 1024 derivative matrices per call", nparam);
-    return MATINV_OK;
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK) rc = check_count("ntarget", ntarget, "targets");
+    if (rc == MATINV_OK && dGrad) rc = check_count("nparam", nparam, "derivative matrices");
+    return rc;
 }
 
 // n <= 96: the gradient form of the multi-target tile kernels. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
@@ -1469,35 +1331,12 @@ int multi_target_grad_host(int n, int ntarget, int nparam, const void *hBs, cons
 {
     const size_t vec = (size_t)n * batch, mat = vec * n, ts = batch * (size_t)ntarget, ys = ts * n;
     const size_t par = hGrad ? batch * (size_t)nparam : 0;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dY = nullptr, *dDM = nullptr, *dGrad = nullptr, *dGradC = nullptr, *dLm = nullptr, *dAl = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
-    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dDM), par * (size_t)n * n * sizeof(T));
-    if (e == hipSuccess && hGrad) e = staging_alloc(reinterpret_cast<void **>(&dGrad), par * sizeof(T));
-    if (e == hipSuccess && hGradC) e = staging_alloc(reinterpret_cast<void **>(&dGradC), vec * sizeof(T));
-    if (e == hipSuccess && hLogml) e = staging_alloc(reinterpret_cast<void **>(&dLm), ts * sizeof(T));
-    if (e == hipSuccess && hAlpha) e = staging_alloc(reinterpret_cast<void **>(&dAl), ys * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dY, hYs, ys * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hGrad) e = hipMemcpy(dDM, hDMs, par * (size_t)n * n * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = multi_target_grad_dispatch<T>(n, ntarget, nparam, dB, dC, dY, dDM, dGrad, dGradC, dLm, dAl, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK && hGrad) e = hipMemcpy(hGrad, dGrad, par * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hGradC) e = hipMemcpy(hGradC, dGradC, vec * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hLogml) e = hipMemcpy(hLogml, dLm, ts * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hAlpha) e = hipMemcpy(hAlpha, dAl, ys * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dY), staging_free(dDM), staging_free(dGrad), staging_free(dGradC), staging_free(dLm);
-    staging_free(dAl), staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "multi_target_grad host<->device");
-    return MATINV_OK;
+    // the derivative matrices are read for grad only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hYs, ys}, {hGrad ? hDMs : nullptr, par * (size_t)n * n}};
+    const StagedOut out[] = {{hGrad, par}, {hGradC, vec}, {hLogml, ts}, {hAlpha, ys}};
+    return run_staged<T>("multi_target_grad", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return multi_target_grad_dispatch<T>(n, ntarget, nparam, i[0], i[1], i[2], i[3], o[0], o[1], o[2], o[3], batch, dInfo, nullptr);
+    });
 }
 
 // ---- batched GP regression with a linear trend (matinv_trend_batched) --------------------------------------------------------------------
@@ -1507,8 +1346,7 @@ int trend_check_args(int dtype, int n, int nbasis, int ntarget, int nquery, cons
                      const void *dLogml, const void *dMean, const void *dVar, size_t batch)
 {
     const bool targets = dBeta || dAlpha || dQuad || dLogml || dMean, queries = dMean || dVar;
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (nbasis < 1 || nbasis > 16) return fail(MATINV_ERR_ARG, "nbasis must be in 1 .. 16 (got %d)", nbasis);
     if (nbasis > n) return fail(MATINV_ERR_ARG, "nbasis=%d exceeds n=%d: H^T M^-1 H would be singular", nbasis, n);
     if (batch == 0) return MATINV_OK;
@@ -1521,11 +1359,10 @@ int trend_check_args(int dtype, int n, int nbasis, int ntarget, int nquery, cons
     if (queries && !dAs) return fail(MATINV_ERR_ARG, "mean or var requested without the query vectors (dAs is null)");
     if (queries && !dGs) return fail(MATINV_ERR_ARG, "mean or var requested without the basis values of the queries (dGs is null)");
     if (dVar && !dEs) return fail(MATINV_ERR_ARG, "var requested without the prior variances (dEs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    if (targets && ntarget > 1024) return fail(MATINV_ERR_UNSUPPORTED, "ntarget=%d exceeds the limit of 1024 targets per call", ntarget);
-    if (queries && nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
-    return MATINV_OK;
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK && targets) rc = check_count("ntarget", ntarget, "targets");
+    if (rc == MATINV_OK && queries) rc = check_count("nquery", nquery, "query points");
+    return rc;
 }
 
 // n <= 96: the trend form of the one-wavefront SPD sweep. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
@@ -1557,54 +1394,38 @@ int trend_host(int n, int nbasis, int ntarget, int nquery, const void *hBs, cons
     const bool targets = hBeta || hAlpha || hQuad || hLogml || hMean, queries = hMean || hVar;
     const size_t K = (size_t)nbasis, vec = (size_t)n * batch, mat = vec * n, ts = targets ? batch * (size_t)ntarget : 0;
     const size_t qs = queries ? batch * (size_t)nquery : 0;
-    // element counts, in the order of the pointer tables below
-    const size_t in_count[7] = {mat, hCs ? vec : 0, vec * K, ts * n, qs * n, qs * K, hVar ? qs : 0};
-    const size_t out_count[7] = {ts * K, batch * K * K, ts * n, ts, ts, hMean ? ts * (size_t)nquery : 0, qs};
-    const void *const in_host[7] = {hBs, hCs, hHs, targets ? hYs : nullptr, queries ? hAs : nullptr, queries ? hGs : nullptr,
-                                    hVar ? hEs : nullptr};
-    void *const out_host[7] = {hBeta, hCovBeta, hAlpha, hQuad, hLogml, hMean, hVar};
-    int rc = check_device();
-    if (rc) return rc;
-    T *din[7] = {}, *dout[7] = {};
-    int *dInfo = nullptr;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 7 && e == hipSuccess; ++i)
-        if (in_host[i]) e = staging_alloc(reinterpret_cast<void **>(&din[i]), in_count[i] * sizeof(T));
-    for (int i = 0; i < 7 && e == hipSuccess; ++i)
-        if (out_host[i]) e = staging_alloc(reinterpret_cast<void **>(&dout[i]), out_count[i] * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    for (int i = 0; i < 7 && e == hipSuccess; ++i)
-        if (din[i]) e = hipMemcpy(din[i], in_host[i], in_count[i] * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        rc = trend_dispatch<T>(n, nbasis, ntarget, nquery, din[0], din[1], din[2], din[3], din[4], din[5], din[6], dout[0], dout[1], dout[2],
-                               dout[3], dout[4], dout[5], dout[6], batch, dInfo, nullptr);
-    for (int i = 0; i < 7 && e == hipSuccess && rc == MATINV_OK; ++i)
-        if (dout[i]) e = hipMemcpy(out_host[i], dout[i], out_count[i] * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    for (int i = 0; i < 7; ++i) staging_free(din[i]), staging_free(dout[i]);
-    staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "trend host<->device");
-    return MATINV_OK;
+    // the targets are read for beta, alpha, quad, logml and mean, the query vectors and their basis values for mean and var, the prior
+    // variances for var only
+    const StagedIn in[] = {{hBs, mat},
+                           {hCs, vec},
+                           {hHs, vec * K},
+                           {targets ? hYs : nullptr, ts * n},
+                           {queries ? hAs : nullptr, qs * n},
+                           {queries ? hGs : nullptr, qs * K},
+                           {hVar ? hEs : nullptr, qs}};
+    const StagedOut out[] = {{hBeta, ts * K}, {hCovBeta, batch * K * K}, {hAlpha, ts * n}, {hQuad, ts}, {hLogml, ts},
+                             {hMean, ts * (size_t)nquery}, {hVar, qs}};
+    return run_staged<T>("trend", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return trend_dispatch<T>(n, nbasis, ntarget, nquery, i[0], i[1], i[2], i[3], i[4], i[5], i[6], o[0], o[1], o[2], o[3], o[4], o[5],
+                                 o[6], batch, dInfo, nullptr);
+    });
 }
 
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
-    if (dtype != MATINV_F64 && dtype != MATINV_F32) return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    if (int rc = check_head("n", n, dtype)) return rc;
     if (batch == 0) return MATINV_OK;
     if (nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 (got %d)", nquery);
     if (nsample < 1) return fail(MATINV_ERR_ARG, "nsample must be >= 1 (got %d)", nsample);
     if (!dBs || !dAs || !dZs) return fail(MATINV_ERR_ARG, "null device pointer");
     if (!dY) return fail(MATINV_ERR_ARG, "no output requested (Y is null)");
     if (dMean && !dDs) return fail(MATINV_ERR_ARG, "mean requested without the observations (dDs is null)");
-    if (batch > 0x7fffffffu) return fail(MATINV_ERR_ARG, "batch %zu exceeds the grid limit; split the call", batch);
-    if (n > 1024) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in (limit 1024)", n);
-    if (nquery > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nquery=%d exceeds the limit of 1024 query points per call", nquery);
-    if (nsample > 1024) return fail(MATINV_ERR_UNSUPPORTED, "nsample=%d exceeds the limit of 1024 samples per call", nsample);
-    return MATINV_OK;
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK) rc = check_count("nquery", nquery, "query points");
+    if (rc == MATINV_OK) rc = check_count("nsample", nsample, "samples");
+    return rc;
 }
 
 // Two launches per k-range chunk: the predictive-covariance route for this n (unchanged), then the colour route for Q on its cov and mean.
@@ -1657,36 +1478,12 @@ int sample_host(int n, int nquery, int nsample, const void *hBs, const void *hCs
                 const void *hZs, void *hY, void *hMean, void *hCov, size_t batch, int *info)
 {
     const size_t vec = (size_t)n * batch, mat = vec * n, qs = batch * (size_t)nquery, qq = qs * (size_t)nquery, ys = qs * (size_t)nsample;
-    int rc = check_device();
-    if (rc) return rc;
-    T *dB = nullptr, *dC = nullptr, *dD = nullptr, *dA = nullptr, *dE = nullptr, *dZ = nullptr, *dY = nullptr, *dMean = nullptr, *dCov = nullptr;
-    int *dInfo = nullptr;
-    hipError_t e = staging_alloc(reinterpret_cast<void **>(&dB), mat * sizeof(T));
-    if (e == hipSuccess && hCs) e = staging_alloc(reinterpret_cast<void **>(&dC), vec * sizeof(T));
-    if (e == hipSuccess && hDs) e = staging_alloc(reinterpret_cast<void **>(&dD), vec * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dA), qs * (size_t)n * sizeof(T));
-    if (e == hipSuccess && hEs) e = staging_alloc(reinterpret_cast<void **>(&dE), qq * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dZ), ys * sizeof(T));
-    if (e == hipSuccess) e = staging_alloc(reinterpret_cast<void **>(&dY), ys * sizeof(T));
-    if (e == hipSuccess && hMean) e = staging_alloc(reinterpret_cast<void **>(&dMean), qs * sizeof(T));
-    if (e == hipSuccess && hCov) e = staging_alloc(reinterpret_cast<void **>(&dCov), qq * sizeof(T));
-    if (e == hipSuccess && info) e = staging_alloc(reinterpret_cast<void **>(&dInfo), batch * sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(dB, hBs, mat * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hCs) e = hipMemcpy(dC, hCs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && hDs) e = hipMemcpy(dD, hDs, vec * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dA, hAs, qs * (size_t)n * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess && dE) e = hipMemcpy(dE, hEs, qq * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dZ, hZs, ys * sizeof(T), hipMemcpyHostToDevice);
-    if (e == hipSuccess) rc = sample_dispatch<T>(n, nquery, nsample, dB, dC, dD, dA, dE, dZ, dY, dMean, dCov, batch, dInfo, nullptr);
-    if (e == hipSuccess && rc == MATINV_OK) e = hipMemcpy(hY, dY, ys * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hMean) e = hipMemcpy(hMean, dMean, qs * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && hCov) e = hipMemcpy(hCov, dCov, qq * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == MATINV_OK && info) e = hipMemcpy(info, dInfo, batch * sizeof(int), hipMemcpyDeviceToHost);
-    staging_free(dB), staging_free(dC), staging_free(dD), staging_free(dA), staging_free(dE), staging_free(dZ), staging_free(dY);
-    staging_free(dMean), staging_free(dCov), staging_free(dInfo);
-    if (rc != MATINV_OK) return rc;
-    if (e != hipSuccess) return fail_hip(e, "sample host<->device");
-    return MATINV_OK;
+    // the observations and the prior covariances go along whenever they are given: without Ds the posterior has zero mean
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hDs, vec}, {hAs, qs * (size_t)n}, {hEs, qq}, {hZs, ys}};
+    const StagedOut out[] = {{hY, ys}, {hMean, qs}, {hCov, qq}};
+    return run_staged<T>("sample", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return sample_dispatch<T>(n, nquery, nsample, i[0], i[1], i[2], i[3], i[4], i[5], o[0], o[1], o[2], batch, dInfo, nullptr);
+    });
 }
 
 template <class T>
@@ -1735,9 +1532,9 @@ int matinv_device_count(void)
 
 int matinv_inverse_batched_host_multi(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info, int nshards)
 {
-    if (dtype == MATINV_F64) return inverse_host_multi<double>(algo, n, hA, hAinv, batch, info, nshards, MATINV_KERNEL_AUTO);
-    if (dtype == MATINV_F32) return inverse_host_multi<float>(algo, n, hA, hAinv, batch, info, nshards, MATINV_KERNEL_AUTO);
-    return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return by_dtype(dtype, [&](auto t) {
+        return inverse_host_multi<decltype(t)>(algo, n, hA, hAinv, batch, info, nshards, MATINV_KERNEL_AUTO);
+    });
 }
 
 int matinv_release_cache(void)
@@ -1831,11 +1628,9 @@ int matinv_device_synchronize(void)
 int matinv_inverse_batched_ex(int algo, int dtype, int n, const void *dA, size_t strideA, void *dAinv,
                               size_t strideInv, size_t batch, int *dInfo, void *stream, int kernel)
 {
-    if (dtype == MATINV_F64)
-        return inverse_strided<double>(algo, n, dA, strideA, dAinv, strideInv, batch, dInfo, stream, kernel);
-    if (dtype == MATINV_F32)
-        return inverse_strided<float>(algo, n, dA, strideA, dAinv, strideInv, batch, dInfo, stream, kernel);
-    return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return by_dtype(dtype, [&](auto t) {
+        return inverse_strided<decltype(t)>(algo, n, dA, strideA, dAinv, strideInv, batch, dInfo, stream, kernel);
+    });
 }
 
 int matinv_inverse_batched(int algo, int dtype, int n, const void *dA, size_t strideA, void *dAinv, size_t strideInv,
@@ -1847,7 +1642,7 @@ int matinv_inverse_batched(int algo, int dtype, int n, const void *dA, size_t st
 
 int matinv_select_kernel(int algo, int dtype, int n)
 {
-    if (n < 1) return fail(MATINV_ERR_ARG, "n must be >= 1 (got %d)", n);
+    if (int rc = check_order("n", n)) return rc;
     int k = (dtype == MATINV_F64) ? select_auto<double>(algo, n) : select_auto<float>(algo, n);
     if (k < 0) return fail(MATINV_ERR_UNSUPPORTED, "n=%d exceeds every kernel family built in", n);
     return k;
@@ -1884,8 +1679,9 @@ int matinv_solve_batched_ex(int algo, int dtype, int n, int nrhs, const void *dA
     int rc = solve_check_args(algo, dtype, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, kernel);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return solve_strided<double>(algo, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, dInfo, st, kernel);
-    return solve_strided<float>(algo, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, dInfo, st, kernel);
+    return by_dtype(dtype, [&](auto t) {
+        return solve_strided<decltype(t)>(algo, n, nrhs, dA, strideA, dB, strideB, dX, strideX, batch, dInfo, st, kernel);
+    });
 }
 
 int matinv_solve_batched(int algo, int dtype, int n, int nrhs, const void *dA, size_t strideA, const void *dB, size_t strideB, void *dX,
@@ -1911,8 +1707,7 @@ int matinv_solve_batched_host(int algo, int dtype, int n, int nrhs, const void *
     int rc = solve_check_args(algo, dtype, n, nrhs, hA, (size_t)n * n, hB, (size_t)n * nrhs, hX, (size_t)n * nrhs, batch,
                               MATINV_KERNEL_AUTO);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return solve_host<double>(algo, n, nrhs, hA, hB, hX, batch, info);
-    return solve_host<float>(algo, n, nrhs, hA, hB, hX, batch, info);
+    return by_dtype(dtype, [&](auto t) { return solve_host<decltype(t)>(algo, n, nrhs, hA, hB, hX, batch, info); });
 }
 
 int matinv_logdet_batched_ex(int algo, int dtype, int n, const void *dA, size_t strideA, void *dLogAbsDet, void *dSign, size_t batch,
@@ -1921,8 +1716,9 @@ int matinv_logdet_batched_ex(int algo, int dtype, int n, const void *dA, size_t 
     int rc = logdet_check_args(algo, dtype, n, dA, strideA, dLogAbsDet, batch, kernel);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return logdet_strided<double>(algo, n, dA, strideA, dLogAbsDet, dSign, batch, dInfo, st, kernel);
-    return logdet_strided<float>(algo, n, dA, strideA, dLogAbsDet, dSign, batch, dInfo, st, kernel);
+    return by_dtype(dtype, [&](auto t) {
+        return logdet_strided<decltype(t)>(algo, n, dA, strideA, dLogAbsDet, dSign, batch, dInfo, st, kernel);
+    });
 }
 
 int matinv_logdet_batched(int algo, int dtype, int n, const void *dA, size_t strideA, void *dLogAbsDet, void *dSign, size_t batch,
@@ -1969,8 +1765,7 @@ int matinv_logdet_batched_host(int algo, int dtype, int n, const void *hA, void 
 {
     int rc = logdet_check_args(algo, dtype, n, hA, (size_t)n * n, hLogAbsDet, batch, MATINV_KERNEL_AUTO);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return logdet_host<double>(algo, n, hA, hLogAbsDet, hSign, batch, info);
-    return logdet_host<float>(algo, n, hA, hLogAbsDet, hSign, batch, info);
+    return by_dtype(dtype, [&](auto t) { return logdet_host<decltype(t)>(algo, n, hA, hLogAbsDet, hSign, batch, info); });
 }
 
 int matinv_logml_batched(int dtype, int n, const void *dBs, const void *dCs, const void *dDs, void *dLogml, size_t batch, int *dInfo,
@@ -1979,16 +1774,14 @@ int matinv_logml_batched(int dtype, int n, const void *dBs, const void *dCs, con
     int rc = logml_check_args(dtype, n, dBs, dDs, dLogml, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return logml_dispatch<double>(n, dBs, dCs, dDs, dLogml, batch, dInfo, st);
-    return logml_dispatch<float>(n, dBs, dCs, dDs, dLogml, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) { return logml_dispatch<decltype(t)>(n, dBs, dCs, dDs, dLogml, batch, dInfo, st); });
 }
 
 int matinv_logml_batched_host(int dtype, int n, const void *hBs, const void *hCs, const void *hDs, void *hLogml, size_t batch, int *info)
 {
     int rc = logml_check_args(dtype, n, hBs, hDs, hLogml, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return logml_host<double>(n, hBs, hCs, hDs, hLogml, batch, info);
-    return logml_host<float>(n, hBs, hCs, hDs, hLogml, batch, info);
+    return by_dtype(dtype, [&](auto t) { return logml_host<decltype(t)>(n, hBs, hCs, hDs, hLogml, batch, info); });
 }
 
 int matinv_loo_batched(int dtype, int n, const void *dBs, const void *dCs, const void *dDs, void *dMean, void *dVar, void *dLogPL, size_t batch,
@@ -1997,13 +1790,12 @@ int matinv_loo_batched(int dtype, int n, const void *dBs, const void *dCs, const
     int rc = loo_check_args(dtype, n, dBs, dDs, dMean, dVar, dLogPL, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return loo_dispatch<double>(n, dBs, dCs, dDs, dMean, dVar, dLogPL, batch, dInfo, st);
-    return loo_dispatch<float>(n, dBs, dCs, dDs, dMean, dVar, dLogPL, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) { return loo_dispatch<decltype(t)>(n, dBs, dCs, dDs, dMean, dVar, dLogPL, batch, dInfo, st); });
 }
 
 const char *matinv_loo_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return loo_tile_supports(n) ? name_loo_tile(dtype == MATINV_F64, n) : name_loo_global(dtype == MATINV_F64);
 }
 
@@ -2012,8 +1804,7 @@ int matinv_loo_batched_host(int dtype, int n, const void *hBs, const void *hCs, 
 {
     int rc = loo_check_args(dtype, n, hBs, hDs, hMean, hVar, hLogPL, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return loo_host<double>(n, hBs, hCs, hDs, hMean, hVar, hLogPL, batch, info);
-    return loo_host<float>(n, hBs, hCs, hDs, hMean, hVar, hLogPL, batch, info);
+    return by_dtype(dtype, [&](auto t) { return loo_host<decltype(t)>(n, hBs, hCs, hDs, hMean, hVar, hLogPL, batch, info); });
 }
 
 int matinv_logml_grad_batched(int dtype, int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad,
@@ -2022,13 +1813,14 @@ int matinv_logml_grad_batched(int dtype, int n, int nparam, const void *dBs, con
     int rc = logml_grad_check_args(dtype, n, nparam, dBs, dDs, dDMs, dGrad, dGradC, dAlpha, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return logml_grad_dispatch<double>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dAlpha, batch, dInfo, st);
-    return logml_grad_dispatch<float>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dAlpha, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return logml_grad_dispatch<decltype(t)>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dAlpha, batch, dInfo, st);
+    });
 }
 
 const char *matinv_logml_grad_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return logml_grad_tile_supports(n) ? name_logml_grad_tile(dtype == MATINV_F64, n) : name_logml_grad_global(dtype == MATINV_F64);
 }
 
@@ -2037,8 +1829,9 @@ int matinv_logml_grad_batched_host(int dtype, int n, int nparam, const void *hBs
 {
     int rc = logml_grad_check_args(dtype, n, nparam, hBs, hDs, hDMs, hGrad, hGradC, hAlpha, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return logml_grad_host<double>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hAlpha, batch, info);
-    return logml_grad_host<float>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hAlpha, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return logml_grad_host<decltype(t)>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hAlpha, batch, info);
+    });
 }
 
 int matinv_predict_batched(int dtype, int n, int nquery, const void *dBs, const void *dCs, const void *dDs, const void *dAs, const void *dEs,
@@ -2047,13 +1840,14 @@ int matinv_predict_batched(int dtype, int n, int nquery, const void *dBs, const 
     int rc = predict_check_args(dtype, n, nquery, dBs, dDs, dAs, dMean, dVar, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return predict_dispatch<double>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dVar, batch, dInfo, st);
-    return predict_dispatch<float>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dVar, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return predict_dispatch<decltype(t)>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dVar, batch, dInfo, st);
+    });
 }
 
 const char *matinv_predict_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return predict_tile_supports(n) ? name_predict_tile(dtype == MATINV_F64, n) : name_predict_global(dtype == MATINV_F64);
 }
 
@@ -2062,8 +1856,7 @@ int matinv_predict_batched_host(int dtype, int n, int nquery, const void *hBs, c
 {
     int rc = predict_check_args(dtype, n, nquery, hBs, hDs, hAs, hMean, hVar, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return predict_host<double>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hVar, batch, info);
-    return predict_host<float>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hVar, batch, info);
+    return by_dtype(dtype, [&](auto t) { return predict_host<decltype(t)>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hVar, batch, info); });
 }
 
 int matinv_predict_cov_batched(int dtype, int n, int nquery, const void *dBs, const void *dCs, const void *dDs, const void *dAs,
@@ -2072,13 +1865,14 @@ int matinv_predict_cov_batched(int dtype, int n, int nquery, const void *dBs, co
     int rc = predict_cov_check_args(dtype, n, nquery, dBs, dDs, dAs, dMean, dCov, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return predict_cov_dispatch<double>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dCov, batch, dInfo, st);
-    return predict_cov_dispatch<float>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dCov, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return predict_cov_dispatch<decltype(t)>(n, nquery, dBs, dCs, dDs, dAs, dEs, dMean, dCov, batch, dInfo, st);
+    });
 }
 
 const char *matinv_predict_cov_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return predict_cov_tile_supports(n) ? name_predict_cov_tile(dtype == MATINV_F64, n) : name_predict_cov_global(dtype == MATINV_F64);
 }
 
@@ -2087,8 +1881,9 @@ int matinv_predict_cov_batched_host(int dtype, int n, int nquery, const void *hB
 {
     int rc = predict_cov_check_args(dtype, n, nquery, hBs, hDs, hAs, hMean, hCov, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return predict_cov_host<double>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
-    return predict_cov_host<float>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return predict_cov_host<decltype(t)>(n, nquery, hBs, hCs, hDs, hAs, hEs, hMean, hCov, batch, info);
+    });
 }
 
 int matinv_colour_batched(int dtype, int q, int nsample, const void *dC, size_t strideC, const void *dM, const void *dZ, void *dY, void *dL,
@@ -2097,13 +1892,14 @@ int matinv_colour_batched(int dtype, int q, int nsample, const void *dC, size_t 
     int rc = colour_check_args(dtype, q, nsample, dC, strideC, dZ, dY, dL, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return colour_dispatch<double>(q, nsample, dC, strideC, dM, dZ, dY, dL, batch, dInfo, 0, st);
-    return colour_dispatch<float>(q, nsample, dC, strideC, dM, dZ, dY, dL, batch, dInfo, 0, st);
+    return by_dtype(dtype, [&](auto t) {
+        return colour_dispatch<decltype(t)>(q, nsample, dC, strideC, dM, dZ, dY, dL, batch, dInfo, 0, st);
+    });
 }
 
 const char *matinv_colour_kernel_name(int dtype, int q)
 {
-    if (q < 1 || q > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, q)) return "";
     return colour_tile_supports(q) ? name_colour_tile(dtype == MATINV_F64, q) : name_colour_global(dtype == MATINV_F64);
 }
 
@@ -2112,8 +1908,7 @@ int matinv_colour_batched_host(int dtype, int q, int nsample, const void *hC, si
 {
     int rc = colour_check_args(dtype, q, nsample, hC, strideC, hZ, hY, hL, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return colour_host<double>(q, nsample, hC, strideC, hM, hZ, hY, hL, batch, info);
-    return colour_host<float>(q, nsample, hC, strideC, hM, hZ, hY, hL, batch, info);
+    return by_dtype(dtype, [&](auto t) { return colour_host<decltype(t)>(q, nsample, hC, strideC, hM, hZ, hY, hL, batch, info); });
 }
 
 int matinv_whiten_batched(int dtype, int q, int npoint, const void *dC, size_t strideC, const void *dM, const void *dX, void *dW, void *dMaha,
@@ -2122,13 +1917,14 @@ int matinv_whiten_batched(int dtype, int q, int npoint, const void *dC, size_t s
     int rc = whiten_check_args(dtype, q, npoint, dC, strideC, dX, dW, dMaha, dLogdet, dLogpdf, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return whiten_dispatch<double>(q, npoint, dC, strideC, dM, dX, dW, dMaha, dLogdet, dLogpdf, batch, dInfo, st);
-    return whiten_dispatch<float>(q, npoint, dC, strideC, dM, dX, dW, dMaha, dLogdet, dLogpdf, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return whiten_dispatch<decltype(t)>(q, npoint, dC, strideC, dM, dX, dW, dMaha, dLogdet, dLogpdf, batch, dInfo, st);
+    });
 }
 
 const char *matinv_whiten_kernel_name(int dtype, int q)
 {
-    if (q < 1 || q > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, q)) return "";
     return whiten_tile_supports(q) ? name_whiten_tile(dtype == MATINV_F64, q) : name_whiten_global(dtype == MATINV_F64);
 }
 
@@ -2137,8 +1933,9 @@ int matinv_whiten_batched_host(int dtype, int q, int npoint, const void *hC, siz
 {
     int rc = whiten_check_args(dtype, q, npoint, hC, strideC, hX, hW, hMaha, hLogdet, hLogpdf, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return whiten_host<double>(q, npoint, hC, strideC, hM, hX, hW, hMaha, hLogdet, hLogpdf, batch, info);
-    return whiten_host<float>(q, npoint, hC, strideC, hM, hX, hW, hMaha, hLogdet, hLogpdf, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return whiten_host<decltype(t)>(q, npoint, hC, strideC, hM, hX, hW, hMaha, hLogdet, hLogpdf, batch, info);
+    });
 }
 
 int matinv_multi_target_batched(int dtype, int n, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dYs, const void *dAs,
@@ -2147,14 +1944,15 @@ int matinv_multi_target_batched(int dtype, int n, int ntarget, int nquery, const
     int rc = multi_target_check_args(dtype, n, ntarget, nquery, dBs, dYs, dAs, dAlpha, dQuad, dLogdet, dLogml, dMean, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64)
-        return multi_target_dispatch<double>(n, ntarget, nquery, dBs, dCs, dYs, dAs, dAlpha, dQuad, dLogdet, dLogml, dMean, batch, dInfo, st);
-    return multi_target_dispatch<float>(n, ntarget, nquery, dBs, dCs, dYs, dAs, dAlpha, dQuad, dLogdet, dLogml, dMean, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return multi_target_dispatch<decltype(t)>(n, ntarget, nquery, dBs, dCs, dYs, dAs, dAlpha, dQuad, dLogdet, dLogml, dMean, batch, dInfo,
+                                                  st);
+    });
 }
 
 const char *matinv_multi_target_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return multi_target_tile_supports(n) ? name_multi_target_tile(dtype == MATINV_F64, n) : name_multi_target_global(dtype == MATINV_F64);
 }
 
@@ -2164,9 +1962,9 @@ int matinv_multi_target_batched_host(int dtype, int n, int ntarget, int nquery, 
 {
     int rc = multi_target_check_args(dtype, n, ntarget, nquery, hBs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64)
-        return multi_target_host<double>(n, ntarget, nquery, hBs, hCs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch, info);
-    return multi_target_host<float>(n, ntarget, nquery, hBs, hCs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return multi_target_host<decltype(t)>(n, ntarget, nquery, hBs, hCs, hYs, hAs, hAlpha, hQuad, hLogdet, hLogml, hMean, batch, info);
+    });
 }
 
 int matinv_multi_target_grad_batched(int dtype, int n, int ntarget, int nparam, const void *dBs, const void *dCs, const void *dYs,
@@ -2176,14 +1974,14 @@ int matinv_multi_target_grad_batched(int dtype, int n, int ntarget, int nparam, 
     int rc = multi_target_grad_check_args(dtype, n, ntarget, nparam, dBs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64)
-        return multi_target_grad_dispatch<double>(n, ntarget, nparam, dBs, dCs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, batch, dInfo, st);
-    return multi_target_grad_dispatch<float>(n, ntarget, nparam, dBs, dCs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return multi_target_grad_dispatch<decltype(t)>(n, ntarget, nparam, dBs, dCs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, batch, dInfo, st);
+    });
 }
 
 const char *matinv_multi_target_grad_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return multi_target_grad_tile_supports(n) ? name_multi_target_grad_tile(dtype == MATINV_F64, n)
                                               : name_multi_target_grad_global(dtype == MATINV_F64);
 }
@@ -2193,9 +1991,9 @@ int matinv_multi_target_grad_batched_host(int dtype, int n, int ntarget, int npa
 {
     int rc = multi_target_grad_check_args(dtype, n, ntarget, nparam, hBs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64)
-        return multi_target_grad_host<double>(n, ntarget, nparam, hBs, hCs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch, info);
-    return multi_target_grad_host<float>(n, ntarget, nparam, hBs, hCs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return multi_target_grad_host<decltype(t)>(n, ntarget, nparam, hBs, hCs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, batch, info);
+    });
 }
 
 int matinv_trend_batched(int dtype, int n, int nbasis, int ntarget, int nquery, const void *dBs, const void *dCs, const void *dHs,
@@ -2206,16 +2004,15 @@ int matinv_trend_batched(int dtype, int n, int nbasis, int ntarget, int nquery, 
                               dVar, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64)
-        return trend_dispatch<double>(n, nbasis, ntarget, nquery, dBs, dCs, dHs, dYs, dAs, dGs, dEs, dBeta, dCovBeta, dAlpha, dQuad, dLogml,
-                                      dMean, dVar, batch, dInfo, st);
-    return trend_dispatch<float>(n, nbasis, ntarget, nquery, dBs, dCs, dHs, dYs, dAs, dGs, dEs, dBeta, dCovBeta, dAlpha, dQuad, dLogml, dMean,
-                                 dVar, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return trend_dispatch<decltype(t)>(n, nbasis, ntarget, nquery, dBs, dCs, dHs, dYs, dAs, dGs, dEs, dBeta, dCovBeta, dAlpha, dQuad, dLogml,
+                                           dMean, dVar, batch, dInfo, st);
+    });
 }
 
 const char *matinv_trend_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return trend_tile_supports(n) ? name_trend_tile(dtype == MATINV_F64, n) : name_trend_global(dtype == MATINV_F64);
 }
 
@@ -2226,11 +2023,10 @@ int matinv_trend_batched_host(int dtype, int n, int nbasis, int ntarget, int nqu
     int rc = trend_check_args(dtype, n, nbasis, ntarget, nquery, hBs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml, hMean,
                               hVar, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64)
-        return trend_host<double>(n, nbasis, ntarget, nquery, hBs, hCs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml,
-                                  hMean, hVar, batch, info);
-    return trend_host<float>(n, nbasis, ntarget, nquery, hBs, hCs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml, hMean,
-                             hVar, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return trend_host<decltype(t)>(n, nbasis, ntarget, nquery, hBs, hCs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml,
+                                       hMean, hVar, batch, info);
+    });
 }
 
 int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dCs, const void *dDs, const void *dAs,
@@ -2239,9 +2035,9 @@ int matinv_sample_batched(int dtype, int n, int nquery, int nsample, const void 
     int rc = sample_check_args(dtype, n, nquery, nsample, dBs, dDs, dAs, dZs, dY, dMean, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64)
-        return sample_dispatch<double>(n, nquery, nsample, dBs, dCs, dDs, dAs, dEs, dZs, dY, dMean, dCov, batch, dInfo, st);
-    return sample_dispatch<float>(n, nquery, nsample, dBs, dCs, dDs, dAs, dEs, dZs, dY, dMean, dCov, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return sample_dispatch<decltype(t)>(n, nquery, nsample, dBs, dCs, dDs, dAs, dEs, dZs, dY, dMean, dCov, batch, dInfo, st);
+    });
 }
 
 int matinv_sample_batched_host(int dtype, int n, int nquery, int nsample, const void *hBs, const void *hCs, const void *hDs, const void *hAs,
@@ -2249,8 +2045,9 @@ int matinv_sample_batched_host(int dtype, int n, int nquery, int nsample, const 
 {
     int rc = sample_check_args(dtype, n, nquery, nsample, hBs, hDs, hAs, hZs, hY, hMean, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return sample_host<double>(n, nquery, nsample, hBs, hCs, hDs, hAs, hEs, hZs, hY, hMean, hCov, batch, info);
-    return sample_host<float>(n, nquery, nsample, hBs, hCs, hDs, hAs, hEs, hZs, hY, hMean, hCov, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return sample_host<decltype(t)>(n, nquery, nsample, hBs, hCs, hDs, hAs, hEs, hZs, hY, hMean, hCov, batch, info);
+    });
 }
 
 int matinv_loo_grad_batched(int dtype, int n, int nparam, const void *dBs, const void *dCs, const void *dDs, const void *dDMs, void *dGrad,
@@ -2259,13 +2056,14 @@ int matinv_loo_grad_batched(int dtype, int n, int nparam, const void *dBs, const
     int rc = loo_grad_check_args(dtype, n, nparam, dBs, dDs, dDMs, dGrad, dGradC, dLogPL, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == MATINV_F64) return loo_grad_dispatch<double>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dLogPL, batch, dInfo, st);
-    return loo_grad_dispatch<float>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dLogPL, batch, dInfo, st);
+    return by_dtype(dtype, [&](auto t) {
+        return loo_grad_dispatch<decltype(t)>(n, nparam, dBs, dCs, dDs, dDMs, dGrad, dGradC, dLogPL, batch, dInfo, st);
+    });
 }
 
 const char *matinv_loo_grad_kernel_name(int dtype, int n)
 {
-    if (n < 1 || n > 1024 || (dtype != MATINV_F64 && dtype != MATINV_F32)) return "";
+    if (!has_kernel_name(dtype, n)) return "";
     return loo_grad_tile_supports(n) ? name_loo_grad_tile(dtype == MATINV_F64, n) : name_loo_grad_global(dtype == MATINV_F64);
 }
 
@@ -2274,47 +2072,38 @@ int matinv_loo_grad_batched_host(int dtype, int n, int nparam, const void *hBs, 
 {
     int rc = loo_grad_check_args(dtype, n, nparam, hBs, hDs, hDMs, hGrad, hGradC, hLogPL, batch);
     if (rc != MATINV_OK || batch == 0) return rc;
-    if (dtype == MATINV_F64) return loo_grad_host<double>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hLogPL, batch, info);
-    return loo_grad_host<float>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hLogPL, batch, info);
+    return by_dtype(dtype, [&](auto t) {
+        return loo_grad_host<decltype(t)>(n, nparam, hBs, hCs, hDs, hDMs, hGrad, hGradC, hLogPL, batch, info);
+    });
 }
 
 int matinv_mean_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dDs,
                         void *dMeans, size_t batch, int *dInfo, void *stream)
 {
-    if (dtype == MATINV_F64) return gp_dispatch<double>(n, dAs, dBs, dCs, dDs, nullptr, dMeans, batch, dInfo, stream, false);
-    if (dtype == MATINV_F32) return gp_dispatch<float>(n, dAs, dBs, dCs, dDs, nullptr, dMeans, batch, dInfo, stream, false);
-    return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return by_dtype(dtype, [&](auto t) { return gp_dispatch<decltype(t)>(n, dAs, dBs, dCs, dDs, nullptr, dMeans, batch, dInfo, stream, false); });
 }
 
 int matinv_variance_batched(int dtype, int n, const void *dAs, const void *dBs, const void *dCs, const void *dEs,
                             void *dVars, size_t batch, int *dInfo, void *stream)
 {
-    if (dtype == MATINV_F64) return gp_dispatch<double>(n, dAs, dBs, dCs, nullptr, dEs, dVars, batch, dInfo, stream, true);
-    if (dtype == MATINV_F32) return gp_dispatch<float>(n, dAs, dBs, dCs, nullptr, dEs, dVars, batch, dInfo, stream, true);
-    return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return by_dtype(dtype, [&](auto t) { return gp_dispatch<decltype(t)>(n, dAs, dBs, dCs, nullptr, dEs, dVars, batch, dInfo, stream, true); });
 }
 
 int matinv_mean_batched_host(int dtype, int n, const void *hAs, const void *hBs, const void *hCs, const void *hDs,
                              void *hMeans, size_t batch, int *info)
 {
-    if (dtype == MATINV_F64) return gp_host<double>(n, hAs, hBs, hCs, hDs, hMeans, batch, info, false);
-    if (dtype == MATINV_F32) return gp_host<float>(n, hAs, hBs, hCs, hDs, hMeans, batch, info, false);
-    return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return by_dtype(dtype, [&](auto t) { return gp_host<decltype(t)>(n, hAs, hBs, hCs, hDs, hMeans, batch, info, false); });
 }
 
 int matinv_variance_batched_host(int dtype, int n, const void *hAs, const void *hBs, const void *hCs, const void *hEs,
                                  void *hVars, size_t batch, int *info)
 {
-    if (dtype == MATINV_F64) return gp_host<double>(n, hAs, hBs, hCs, hEs, hVars, batch, info, true);
-    if (dtype == MATINV_F32) return gp_host<float>(n, hAs, hBs, hCs, hEs, hVars, batch, info, true);
-    return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return by_dtype(dtype, [&](auto t) { return gp_host<decltype(t)>(n, hAs, hBs, hCs, hEs, hVars, batch, info, true); });
 }
 
 int matinv_inverse_batched_host(int algo, int dtype, int n, const void *hA, void *hAinv, size_t batch, int *info)
 {
-    if (dtype == MATINV_F64) return inverse_host<double>(algo, n, hA, hAinv, batch, info, nullptr);
-    if (dtype == MATINV_F32) return inverse_host<float>(algo, n, hA, hAinv, batch, info, nullptr);
-    return fail(MATINV_ERR_ARG, "unknown dtype %d", dtype);
+    return by_dtype(dtype, [&](auto t) { return inverse_host<decltype(t)>(algo, n, hA, hAinv, batch, info, nullptr); });
 }
 
 // ------------------------------------------------------------------------------------------------
