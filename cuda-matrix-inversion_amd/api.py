@@ -1288,6 +1288,115 @@ def trend_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_trend_kernel_name(code, n).decode()
 
 
+_TREND_GRAD_OUTPUTS = ("grad", "gradc", "logml", "alpha", "beta")
+
+
+def _trend_grad_plan(n, batch, asked, numel, Hs, Ys, dMs, nbasis, ntarget, nparam):
+    """the counts and output sizes of a trend gradient request: (nbasis, ntarget, nparam, sizes); `numel` counts a tensor's or array's
+    elements"""
+    if not any(asked.values()):
+        raise ValueError("no output requested")
+    if Hs is None:
+        raise ValueError("the basis vectors Hs are needed")
+    if Ys is None:
+        raise ValueError("every output needs the targets Ys")
+    if asked["grad"] and dMs is None:
+        raise ValueError("grad needs the derivative matrices dMs")
+    if nbasis is None:
+        nbasis = numel(Hs) // (batch * n) if batch else 1
+    if not 1 <= nbasis <= 16 or nbasis > n:
+        raise ValueError(f"nbasis must be in 1 .. min(16, n) (got {nbasis})")
+    if ntarget is None:
+        ntarget = numel(Ys) // (batch * n) if batch else 0
+    if not asked["grad"]:
+        nparam = 0
+    elif nparam is None:
+        nparam = numel(dMs) // (batch * n * n) if batch else 0
+    if batch and numel(Hs) < batch * nbasis * n:
+        raise ValueError("Hs needs batch*K*n elements")
+    if batch and (ntarget < 1 or numel(Ys) < batch * ntarget * n):
+        raise ValueError("Ys needs batch*D*n elements, D >= 1")
+    if asked["grad"] and batch and (nparam < 1 or numel(dMs) < batch * nparam * n * n):
+        raise ValueError("dMs needs batch*P*n*n elements, P >= 1")
+    sizes = dict(grad=batch * nparam, gradc=batch * n, logml=batch * ntarget, alpha=batch * ntarget * n, beta=batch * ntarget * nbasis)
+    return nbasis, ntarget, nparam, sizes
+
+
+def trend_grad_batched(n, Bs, Cs, Hs, Ys, dMs, grad=None, gradc=None, logml=None, alpha=None, beta=None, batchSize=None, info=None,
+                       want=("grad",), nbasis=None, ntarget=None, nparam=None):
+    """Gradients of the restricted (REML) log marginal likelihood of a GP with a linear trend on device tensors
+    (matinv_trend_grad_batched; asynchronous on torch's current stream): the gradient of sum_t logml[k, t] of trend_batched, from one
+    factorisation. With M_k = B_k + diag c_k, Kinv = M_k^-1, H the K basis vectors, A = H^T Kinv H, P = Kinv - Kinv H A^-1 H^T Kinv,
+    alpha_t = P y_kt for the D targets and G = sum_t alpha_t alpha_t^T - D P:
+        grad[k, p] = 1/2 sum_ij G_ij dM_p[i, j],  gradc[k, i] = 1/2 G_ii,  logml[k, t], alpha[k, t], beta[k, t] as trend_batched (bit for bit)
+    Hs, Ys as in trend_batched; dMs: batchSize*P*n*n elements, matrix (k, p) at (k*P + p)*n*n, column-major, lower triangle read. grad is
+    batchSize*P, gradc batchSize*n, logml batchSize*D, alpha batchSize*D*n, beta batchSize*D*K. K, D and P are inferred from Hs.numel(),
+    Ys.numel() and dMs.numel() unless `nbasis` / `ntarget` / `nparam` are given; 1 <= K <= min(16, n).
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one; which are asked for
+    changes no bit of the others. Cs may be None (M = B), dMs may be None when grad is not asked for. Only the lower triangles of B and
+    dM are read and no input is modified. info = the 1-based column of the first non-positive pivot of M, or n + b for the first
+    non-positive pivot b of A (H rank deficient); every requested output of that matrix is then NaN.
+    Returns (grad, gradc, logml, alpha, beta), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Hs, Ys, dMs, grad, gradc, logml, alpha, beta, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    unknown = set(want) - set(_TREND_GRAD_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_TREND_GRAD_OUTPUTS}")
+    given = dict(grad=grad, gradc=gradc, logml=logml, alpha=alpha, beta=beta)
+    asked = {k: given[k] is not None or k in want for k in _TREND_GRAD_OUTPUTS}
+    nbasis, ntarget, nparam, sizes = _trend_grad_plan(n, batchSize, asked, lambda t: t.numel(), Hs, Ys, dMs, nbasis, ntarget, nparam)
+    for k in _TREND_GRAD_OUTPUTS:
+        if asked[k] and given[k] is None:
+            given[k] = torch.empty(sizes[k], dtype=Bs.dtype, device=Bs.device)
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Hs, Ys, dMs, *given.values())):
+        raise TypeError("Bs, Cs, Hs, Ys, dMs and the outputs must have one dtype")
+    if (Cs is not None and Cs.numel() < batchSize * n) or \
+            any(given[k] is not None and given[k].numel() < sizes[k] for k in _TREND_GRAD_OUTPUTS):
+        raise ValueError("Cs needs batchSize*n elements, grad batchSize*P, gradc batchSize*n, logml batchSize*D, alpha batchSize*D*n, "
+                         "beta batchSize*D*K")
+    _check_info(info, batchSize)
+    p = _tensor_ptr
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_trend_grad_batched(
+            _torch_dtype_code(Bs), n, nbasis, ntarget, nparam, p(Bs), p(Cs), p(Hs), p(Ys), p(dMs) if asked["grad"] else None,
+            *(p(given[k]) for k in _TREND_GRAD_OUTPUTS), batchSize, p(info), _stream_ptr(Bs)))
+    return tuple(given[k] for k in _TREND_GRAD_OUTPUTS)
+
+
+def trend_grad_batched_host(n, Bs: np.ndarray, Cs, Hs, Ys, dMs, want=_TREND_GRAD_OUTPUTS, nbasis=None, ntarget=None, nparam=None):
+    """matinv_trend_grad_batched_host on numpy batches (packed; Cs may be None, dMs may be None without "grad" in want, which the default
+    `want` then drops): returns (grad, gradc, logml, alpha, beta, info), None for the outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Cs, Hs, Ys, dMs = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Hs, Ys, dMs))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Hs, Ys, dMs)):
+        raise TypeError("Bs, Cs, Hs, Ys and dMs must have one dtype")
+    if want is _TREND_GRAD_OUTPUTS and dMs is None:
+        want = _TREND_GRAD_OUTPUTS[1:]
+    unknown = set(want) - set(_TREND_GRAD_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_TREND_GRAD_OUTPUTS}")
+    batch = Bs.size // (n * n)
+    asked = {k: k in want for k in _TREND_GRAD_OUTPUTS}
+    nbasis, ntarget, nparam, sizes = _trend_grad_plan(n, batch, asked, lambda a: a.size, Hs, Ys, dMs, nbasis, ntarget, nparam)
+    if Cs is not None and Cs.size < batch * n:
+        raise ValueError("Cs smaller than batch*n")
+    out = {k: np.empty(sizes[k], dtype=Bs.dtype) if asked[k] else None for k in _TREND_GRAD_OUTPUTS}
+    info = np.zeros(batch, dtype=np.int32)
+    p = _array_ptr
+    _lib.check(_lib.lib().matinv_trend_grad_batched_host(
+        _np_dtype_code(Bs.dtype), n, nbasis, ntarget, nparam, p(Bs), p(Cs), p(Hs), p(Ys), p(dMs) if asked["grad"] else None,
+        *(p(out[k]) for k in _TREND_GRAD_OUTPUTS), batch, p(info)))
+    return (*(out[k] for k in _TREND_GRAD_OUTPUTS), info)
+
+
+def trend_grad_kernel_name(dtype, n: int) -> str:
+    """matinv_trend_grad_kernel_name: the kernel a trend gradient request launches ("" when the request would be refused)."""
+    code = _dtype_code(dtype)
+    return _lib.lib().matinv_trend_grad_kernel_name(code, n).decode()
+
+
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")
 
 

@@ -1411,6 +1411,66 @@ int trend_host(int n, int nbasis, int ntarget, int nquery, const void *hBs, cons
     });
 }
 
+// ---- gradients of the restricted log marginal likelihood of the trend model (matinv_trend_grad_batched) ----------------------------------
+// the checks of trend_check_args, in its order, with the lines of multi_target_grad_check_args for nparam and dDMs; every output needs the
+// targets
+int trend_grad_check_args(int dtype, int n, int nbasis, int ntarget, int nparam, const void *dBs, const void *dHs, const void *dYs,
+                          const void *dDMs, const void *dGrad, const void *dGradC, const void *dLogml, const void *dAlpha, const void *dBeta,
+                          size_t batch)
+{
+    if (int rc = check_head("n", n, dtype)) return rc;
+    if (nbasis < 1 || nbasis > 16) return fail(MATINV_ERR_ARG, "nbasis must be in 1 .. 16 (got %d)", nbasis);
+    if (nbasis > n) return fail(MATINV_ERR_ARG, "nbasis=%d exceeds n=%d: H^T M^-1 H would be singular", nbasis, n);
+    if (batch == 0) return MATINV_OK;
+    if (ntarget < 1) return fail(MATINV_ERR_ARG, "ntarget must be >= 1 (got %d)", ntarget);
+    if (nparam < 0 || (dGrad && nparam < 1)) return fail(MATINV_ERR_ARG, "nparam must be >= 1 with grad, >= 0 without (got %d)", nparam);
+    if (!dBs || !dHs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dGrad && !dGradC && !dLogml && !dAlpha && !dBeta)
+        return fail(MATINV_ERR_ARG, "no output requested (grad, gradc, logml, alpha and beta are all null)");
+    if (!dYs) return fail(MATINV_ERR_ARG, "the targets are needed for every output (dYs is null)");
+    if (dGrad && !dDMs) return fail(MATINV_ERR_ARG, "grad requested without derivative matrices (dDMs is null)");
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK) rc = check_count("ntarget", ntarget, "targets");
+    if (rc == MATINV_OK && dGrad) rc = check_count("nparam", nparam, "derivative matrices");
+    return rc;
+}
+
+// n <= 96: the gradient form of the trend tile kernels. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
+template <class T>
+int trend_grad_dispatch(int n, int nbasis, int ntarget, int nparam, const void *dBs, const void *dCs, const void *dHs, const void *dYs,
+                        const void *dDMs, void *dGrad, void *dGradC, void *dLogml, void *dAlpha, void *dBeta, size_t batch, int *dInfo,
+                        hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *h = static_cast<const T *>(dHs);
+    const T *y = static_cast<const T *>(dYs);
+    const T *dM = dGrad ? static_cast<const T *>(dDMs) : nullptr;  // not read without grad
+    T *grad = static_cast<T *>(dGrad), *gradc = static_cast<T *>(dGradC), *lm = static_cast<T *>(dLogml), *al = static_cast<T *>(dAlpha);
+    T *be = static_cast<T *>(dBeta);
+    const hipError_t e =
+        trend_grad_tile_supports(n)
+            ? launch_trend_grad_tile<T>(n, nbasis, ntarget, nparam, B, c, h, y, dM, grad, gradc, lm, al, be, batch, dInfo, stream)
+            : launch_trend_grad_global<T>(n, nbasis, ntarget, nparam, B, c, h, y, dM, grad, gradc, lm, al, be, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "trend_grad launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int trend_grad_host(int n, int nbasis, int ntarget, int nparam, const void *hBs, const void *hCs, const void *hHs, const void *hYs,
+                    const void *hDMs, void *hGrad, void *hGradC, void *hLogml, void *hAlpha, void *hBeta, size_t batch, int *info)
+{
+    const size_t K = (size_t)nbasis, vec = (size_t)n * batch, mat = vec * n, ts = batch * (size_t)ntarget, ys = ts * n;
+    const size_t par = hGrad ? batch * (size_t)nparam : 0;
+    // the derivative matrices are read for grad only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hHs, vec * K}, {hYs, ys}, {hGrad ? hDMs : nullptr, par * (size_t)n * n}};
+    const StagedOut out[] = {{hGrad, par}, {hGradC, vec}, {hLogml, ts}, {hAlpha, ys}, {hBeta, ts * K}};
+    return run_staged<T>("trend_grad", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return trend_grad_dispatch<T>(n, nbasis, ntarget, nparam, i[0], i[1], i[2], i[3], i[4], o[0], o[1], o[2], o[3], o[4], batch, dInfo,
+                                      nullptr);
+    });
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -2026,6 +2086,37 @@ int matinv_trend_batched_host(int dtype, int n, int nbasis, int ntarget, int nqu
     return by_dtype(dtype, [&](auto t) {
         return trend_host<decltype(t)>(n, nbasis, ntarget, nquery, hBs, hCs, hHs, hYs, hAs, hGs, hEs, hBeta, hCovBeta, hAlpha, hQuad, hLogml,
                                        hMean, hVar, batch, info);
+    });
+}
+
+int matinv_trend_grad_batched(int dtype, int n, int nbasis, int ntarget, int nparam, const void *dBs, const void *dCs, const void *dHs,
+                              const void *dYs, const void *dDMs, void *dGrad, void *dGradC, void *dLogml, void *dAlpha, void *dBeta,
+                              size_t batch, int *dInfo, void *stream)
+{
+    int rc = trend_grad_check_args(dtype, n, nbasis, ntarget, nparam, dBs, dHs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, dBeta, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return by_dtype(dtype, [&](auto t) {
+        return trend_grad_dispatch<decltype(t)>(n, nbasis, ntarget, nparam, dBs, dCs, dHs, dYs, dDMs, dGrad, dGradC, dLogml, dAlpha, dBeta,
+                                                batch, dInfo, st);
+    });
+}
+
+const char *matinv_trend_grad_kernel_name(int dtype, int n)
+{
+    if (!has_kernel_name(dtype, n)) return "";
+    return trend_grad_tile_supports(n) ? name_trend_grad_tile(dtype == MATINV_F64, n) : name_trend_grad_global(dtype == MATINV_F64);
+}
+
+int matinv_trend_grad_batched_host(int dtype, int n, int nbasis, int ntarget, int nparam, const void *hBs, const void *hCs, const void *hHs,
+                                   const void *hYs, const void *hDMs, void *hGrad, void *hGradC, void *hLogml, void *hAlpha, void *hBeta,
+                                   size_t batch, int *info)
+{
+    int rc = trend_grad_check_args(dtype, n, nbasis, ntarget, nparam, hBs, hHs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, hBeta, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return trend_grad_host<decltype(t)>(n, nbasis, ntarget, nparam, hBs, hCs, hHs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, hBeta, batch,
+                                            info);
     });
 }
 

@@ -497,6 +497,21 @@ hipError_t launch_trend_global(int n, int nbasis, int ntarget, int nquery, const
                                hipStream_t stream);
 const char *name_trend_global(bool f64);
 
+// Gradients of the restricted log marginal likelihood of the trend model (matinv_trend_grad_batched): Bs, Cs, Hs, Ys as above, dMs as for
+// matinv_logml_grad_batched; grad: batch * nparam, gradc: batch * n, Lm: batch * ntarget, Al: as Ys, Be: batch * ntarget * nbasis. Every
+// output is optional; dMs is read with grad only.
+// (a) the gradient form of the trend tile kernels, n <= 96 (trend_grad_tile_kernels.hip, trend_grad_tile_f32_kernels.hip)
+bool trend_grad_tile_supports(int n);
+template <class T>
+hipError_t launch_trend_grad_tile(int n, int nbasis, int ntarget, int nparam, const T *Bs, const T *Cs, const T *Hs, const T *Ys,
+                                  const T *dMs, T *grad, T *gradc, T *Lm, T *Al, T *Be, size_t batch, int *info, hipStream_t stream);
+const char *name_trend_grad_tile(bool f64, int n);
+// (b) the trend gradient form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_trend_grad_global(int n, int nbasis, int ntarget, int nparam, const T *Bs, const T *Cs, const T *Hs, const T *Ys,
+                                    const T *dMs, T *grad, T *gradc, T *Lm, T *Al, T *Be, size_t batch, int *info, hipStream_t stream);
+const char *name_trend_grad_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

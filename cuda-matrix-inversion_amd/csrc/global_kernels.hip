@@ -1714,4 +1714,266 @@ const char *name_trend_global(bool f64)
                : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true>";
 }
 
+// ---- gradients of the restricted log marginal likelihood of the trend model, 96 < n <= 1024 (matinv_trend_grad_batched behind
+// trend_grad_tile_impl.hpp) ---------------------------------------------------------------------------------------------------------------
+// The trend gradient form of matinv_chol_global: one more template argument again ("Gradients of the restricted log marginal
+// likelihood"). The factorisation, the diagonal fold, the substitutions on [H | Y], A = H^T Kinv H, its factor, beta and alpha are those of
+// the trend form above, so logml, alpha and beta are its values; Kinv h_b and alpha_t stay in scratch behind the factor. Then, when grad
+// or gradc is asked for, L <- L^-1 and Kinv over it in place as in the multi-target gradient form, L_A^-1 column by column, and
+// V = Kinv H L_A^-T over Kinv H, one thread per row, b descending (V_ib needs the columns b' <= b only). With
+//     G_rc = sum_t alpha_tr alpha_tc - D (Kinv_rc - sum_b V_rb V_cb)          (t and b ascending)
+// formed on the fly: gradc_i = 1/2 G_ii, grad_p = sum_{r >= c} w_rc G_rc dM_p[r][c], w = 1/2 on the diagonal, 1 below, summed per thread
+// in element order, then on the fixed LDS tree. info and the NaN outputs as in the trend form. Correct first; speed is not a goal here.
+// Workgroup blockIdx.x serves matrix first + blockIdx.x; `per` = n^2 + n (K + D) + K D elements of workspace each.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR, bool WHITEN, bool MULTI, bool MTGRAD, bool TREND,
+          bool TRENDGRAD>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Hs, const T *Ys, const T *dMs, int nbasis,
+                                                                 int ntarget, int nparam, T *grad, T *gradc, T *Lm, T *Al, T *Be, int *info,
+                                                                 int n, T *workspace, size_t per, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR && WHITEN && MULTI && MTGRAD && TREND && TRENDGRAD,
+                  "the twelve-argument form is the trend gradient kernel");
+    __shared__ T col[1024];
+    __shared__ T sA[16 * 17], sLi[16 * 17];
+    __shared__ T s_ld, s_ldA;
+    __shared__ int s_abad;
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    const size_t nn = (size_t)n * n, K = (size_t)nbasis, nd = (size_t)ntarget;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *V = W + nn;             // Kinv h_b, b < K, then Kinv y_t -> alpha_t
+    T *Bt = V + (K + nd) * n;  // beta_t
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    __syncthreads();
+    int bad = gl_chol_factor(W, n, col);
+    if (!bad) {  // block-uniform
+        if (t == 0) {
+            PivotProduct<T> prod;
+            for (int i = 0; i < n; ++i) prod.fold(W[(size_t)i * n + i]);
+            s_ld = (T)2 * prod.log_value();
+        }
+        for (size_t s = t; s < K + nd; s += GL_THREADS) {
+            const T *x = s < K ? Hs + (k_mat * K + s) * n : Ys + (k_mat * nd + (s - K)) * n;
+            T *v = V + s * n;
+            for (int i = 0; i < n; ++i) v[i] = x[i];
+            for (int k = 0; k < n; ++k) {
+                const T *lk = W + (size_t)k * n;
+                const T w = v[k] / lk[k];
+                v[k] = w;
+                for (int i = k + 1; i < n; ++i) v[i] -= lk[i] * w;
+            }
+            for (int k = n - 1; k >= 0; --k) {
+                const T *lk = W + (size_t)k * n;
+                T a = v[k];
+                for (int i = k + 1; i < n; ++i) a -= lk[i] * v[i];
+                v[k] = a / lk[k];
+            }
+        }
+        __syncthreads();  // Kinv [H | Y] is in V
+        for (size_t e = t; e < K * K; e += GL_THREADS) {
+            const size_t b = e / K, b2 = e - b * K;
+            if (b < b2) continue;
+            const T *h = Hs + (k_mat * K + b) * n, *v = V + b2 * n;
+            T a = 0;
+            for (int i = 0; i < n; ++i) a += h[i] * v[i];
+            sA[b * 17 + b2] = a;
+        }
+        __syncthreads();
+        if (t == 0) {  // A = L_A L_A^T in place, 1 / L_bb on the diagonal (the trend form)
+            int abad = 0;
+            PivotProduct<T> prod;
+            for (int j = 0; j < nbasis; ++j) {
+                const T d = sA[j * 17 + j];
+                if (!(d > (T)0) && abad == 0) abad = j + 1;
+                prod.fold(d);
+                const T rs = (T)1 / sqrt(d);
+                for (int jj = j + 1; jj < nbasis; ++jj) {
+                    const T m = sA[jj * 17 + j] / d;
+                    for (int i = jj; i < nbasis; ++i) sA[i * 17 + jj] -= sA[i * 17 + j] * m;
+                }
+                sA[j * 17 + j] = rs;
+                for (int i = j + 1; i < nbasis; ++i) sA[i * 17 + j] *= rs;
+            }
+            s_abad = abad;
+            s_ldA = prod.log_value();
+        }
+        __syncthreads();
+        if (s_abad) bad = n + s_abad;
+    }
+    if (bad) {  // block-uniform
+        if (Be)
+            for (size_t e = t; e < nd * K; e += GL_THREADS) Be[k_mat * nd * K + e] = nan_of<T>();
+        if (Al)
+            for (size_t e = t; e < nd * n; e += GL_THREADS) Al[k_mat * nd * n + e] = nan_of<T>();
+        if (Lm)
+            for (size_t s = t; s < nd; s += GL_THREADS) Lm[k_mat * nd + s] = nan_of<T>();
+        if (gradc)
+            for (int i = t; i < n; i += GL_THREADS) gradc[k_mat * n + i] = nan_of<T>();
+        if (grad)
+            for (int p = t; p < nparam; p += GL_THREADS) grad[k_mat * nparam + p] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    const T ld = s_ld, ldA = s_ldA;
+    for (size_t s = t; s < nd; s += GL_THREADS) {
+        const T *y = Ys + (k_mat * nd + s) * n;
+        T *v = V + (K + s) * n, *be = Bt + s * K;
+        for (size_t b = 0; b < K; ++b) {
+            const T *kh = V + b * n;
+            T a = 0;
+            for (int i = 0; i < n; ++i) a += kh[i] * y[i];
+            be[b] = a;
+        }
+        for (int i = 0; i < nbasis; ++i) {
+            T a = be[i];
+            for (int k = 0; k < i; ++k) a -= sA[i * 17 + k] * be[k];
+            be[i] = a * sA[i * 17 + i];
+        }
+        for (int i = nbasis - 1; i >= 0; --i) {
+            T a = be[i];
+            for (int k = nbasis - 1; k > i; --k) a -= sA[k * 17 + i] * be[k];
+            be[i] = a * sA[i * 17 + i];
+        }
+        for (size_t b = 0; b < K; ++b) {
+            const T *kh = V + b * n;
+            const T bb = be[b];
+            for (int i = 0; i < n; ++i) v[i] -= kh[i] * bb;
+        }
+        T qd = 0;
+        for (int i = 0; i < n; ++i) qd += y[i] * v[i];
+        if (Be)
+            for (size_t b = 0; b < K; ++b) Be[(k_mat * nd + s) * K + b] = be[b];
+        if (Al)
+            for (int i = 0; i < n; ++i) Al[(k_mat * nd + s) * n + i] = v[i];
+        // log 2 pi
+        if (Lm) Lm[k_mat * nd + s] = (T)-0.5 * ((qd + (ld + ldA)) + (T)(n - nbasis) * (T)1.83787706640934548356);
+    }
+    if (grad || gradc) {  // block-uniform
+        __syncthreads();  // every target's alpha is in V behind Kinv H, and the factor is no longer needed
+        for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+            const T ajj = (T)1 / W[(size_t)j * n + j];
+            for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+            __syncthreads();
+            for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+                T s = 0;
+                for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+                W[(size_t)j * n + i] = -s * ajj;
+            }
+            if (t == 0) W[(size_t)j * n + j] = ajj;
+            __syncthreads();
+        }
+        // column c of Kinv over column c of L^-1; the columns beyond c are still those of L^-1
+        for (int c = 0; c < n; ++c) {
+            for (int k = c + t; k < n; k += GL_THREADS) col[k] = W[(size_t)c * n + k];
+            __syncthreads();
+            for (int r = c + t; r < n; r += GL_THREADS) {
+                T s = 0;
+                if (r == c) {
+                    for (int k = r; k < n; ++k) s += col[k] * col[k];
+                } else {
+                    for (int k = r; k < n; ++k) s += W[(size_t)r * n + k] * col[k];
+                }
+                W[(size_t)c * n + r] = s;
+            }
+            __syncthreads();
+        }
+        if (t < nbasis) {  // column t of L_A^-1 (the trend form's, for covbeta)
+            for (int i = 0; i < nbasis; ++i) {
+                T s = i == t ? (T)1 : (T)0;
+                for (int k = 0; k < i; ++k) s -= sA[i * 17 + k] * sLi[k * 17 + t];
+                sLi[i * 17 + t] = s * sA[i * 17 + i];
+            }
+        }
+        __syncthreads();
+        // V = Kinv H L_A^-T over Kinv H: V_ib = sum_{b' <= b} (Kinv H)_ib' L_A^-1[b][b'], b descending, b' ascending
+        for (int i = t; i < n; i += GL_THREADS)
+            for (int b = nbasis - 1; b >= 0; --b) {
+                T s = 0;
+                for (int b2 = 0; b2 <= b; ++b2) s += V[(size_t)b2 * n + i] * sLi[b * 17 + b2];
+                V[(size_t)b * n + i] = s;
+            }
+        __syncthreads();
+        const T dscale = (T)ntarget;
+        const T *Va = V + K * n;  // alpha_t
+        if (gradc)
+            for (int i = t; i < n; i += GL_THREADS) {
+                T aa = 0, uu = 0;
+                for (size_t s = 0; s < nd; ++s) aa += Va[s * n + i] * Va[s * n + i];
+                for (size_t b = 0; b < K; ++b) uu += V[b * n + i] * V[b * n + i];
+                gradc[k_mat * n + i] = (T)0.5 * (aa - dscale * (W[(size_t)i * n + i] - uu));
+            }
+        if (grad) {
+            for (int p = 0; p < nparam; ++p) {
+                const T *D = dMs + (k_mat * nparam + p) * nn;
+                T s = 0;
+                for (size_t e = t; e < nn; e += GL_THREADS) {
+                    const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+                    if (r < c) continue;
+                    T aa = 0, uu = 0;
+                    for (size_t u = 0; u < nd; ++u) aa += Va[u * n + r] * Va[u * n + c];
+                    for (size_t b = 0; b < K; ++b) uu += V[b * n + r] * V[b * n + c];
+                    const T g = aa - dscale * (W[e] - uu);
+                    s += (r == c ? (T)0.5 : (T)1) * g * D[e];
+                }
+                // block sum on a fixed tree
+                col[t] = s;
+                __syncthreads();
+                for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+                    if (t < off) col[t] += col[t + off];
+                    __syncthreads();
+                }
+                if (t == 0) grad[k_mat * nparam + p] = col[0];
+                __syncthreads();
+            }
+        }
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_trend_grad_global(int n, int nbasis, int ntarget, int nparam, const T *Bs, const T *Cs, const T *Hs, const T *Ys,
+                                    const T *dMs, T *grad, T *gradc, T *Lm, T *Al, T *Be, size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_trend_global)
+    const size_t nd = (size_t)ntarget, K = (size_t)nbasis;
+    const size_t per = (size_t)n * n + (size_t)n * (K + nd) + K * nd;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true, true, true, true, true, true>), dim3((unsigned)cnt),
+                           dim3(GL_THREADS), 0, stream, Bs, Cs, Hs, Ys, dMs, nbasis, ntarget, nparam, grad, gradc, Lm, Al, Be, info, n, ws,
+                           per, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_trend_grad_global<double>(int, int, int, int, const double *, const double *, const double *, const double *,
+                                                     const double *, double *, double *, double *, double *, double *, size_t, int *,
+                                                     hipStream_t);
+template hipError_t launch_trend_grad_global<float>(int, int, int, int, const float *, const float *, const float *, const float *,
+                                                    const float *, float *, float *, float *, float *, float *, size_t, int *, hipStream_t);
+
+const char *name_trend_grad_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true, true>";
+}
+
 }  // namespace matinv

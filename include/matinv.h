@@ -445,6 +445,38 @@ int matinv_trend_batched_host(int dtype, int n, int nbasis, int ntarget, int nqu
                               const void *hYs, const void *hAs, const void *hGs, const void *hEs, void *hBeta, void *hCovBeta, void *hAlpha,
                               void *hQuad, void *hLogml, void *hMean, void *hVar, size_t batch, int *info);
 
+/* Gradients of the restricted (REML) log marginal likelihood of the trend model, device-resident: the gradient of sum_t logml_kt of
+ * matinv_trend_batched, from one factorisation. With M_k = B_k + diag(c_k), Kinv = M_k^-1, H the K = nbasis basis vectors,
+ * A = H^T Kinv H, P = Kinv - Kinv H A^-1 H^T Kinv, D = ntarget targets y_kt, alpha_t = P y_kt, nparam symmetric derivative matrices dM_p
+ * per matrix and G = sum_t alpha_t alpha_t^T - D P (H does not depend on the parameters):
+ *   grad[k*nparam + p]            = 1/2 sum_ij G_ij dM_p[i][j]                   d(sum_t logml_t) / d theta_p
+ *   gradc[k*n + i]                = 1/2 G_ii                                     d(sum_t logml_t) / d c_i
+ *   logml[k*ntarget + t], alpha[(k*ntarget + t)*n + i], beta[(k*ntarget + t)*K + b]    as matinv_trend_batched
+ * dBs, dCs, dHs, dYs as in matinv_trend_batched (only the lower triangle of B read; dCs may be NULL); dDMs as in
+ * matinv_logml_grad_batched (matrix (k, p) at (k*nparam + p)*n*n, only its lower triangle read). Every output is optional and at least
+ * one is required (all NULL: MATINV_ERR_ARG); which of them are requested does not change a bit of the others. dGrad needs nparam >= 1
+ * and dDMs; without it nparam may be 0, dDMs NULL, and dDMs is not read. ntarget >= 1, dYs and dHs are always needed. 1 <= n <= 1024;
+ * 1 <= nbasis <= 16 and nbasis <= n (otherwise MATINV_ERR_ARG, checked with n and dtype); ntarget <= 1024, nparam <= 1024 (beyond:
+ * MATINV_ERR_UNSUPPORTED, after the pointer checks); batch < 2^31; batch == 0 is a no-op after the dtype, n and nbasis checks. No input
+ * is modified (outputs must not overlap inputs); neither M, its inverse nor its factor is written to caller memory. logml, alpha and
+ * beta carry the bits matinv_trend_batched gives for the same inputs. dInfo (optional): as matinv_trend_batched: 0, the 1-based column
+ * of the first non-positive (or NaN) pivot of M, or n + b for the first non-positive (or NaN) pivot b of A; on a non-zero info every
+ * requested output of that matrix is NaN; there is no fallback launch. n <= 96: the gradient form of the trend tile sweep: the trend
+ * epilogue without queries, then U = Kinv H L_A^-T on the MFMA unit, -P = -Kinv + U U^T and G over it in the registers by rank-16 MFMA
+ * updates, contracted with each dM_p streamed once (n^2/2 + n + K n + D n + nparam n^2/2 elements read, nparam + n + D + D n + D K
+ * written; with D > 16 alpha is read back once, from dAlpha or from D n elements of library scratch per workgroup). Beyond, to n = 1024:
+ * the trend gradient form of the global-memory Cholesky kernel on a working copy per matrix in library scratch (k-range chunks under
+ * MATINV_BLOCKED_WS_MB). Asynchronous, no host synchronisation. */
+int matinv_trend_grad_batched(int dtype, int n, int nbasis, int ntarget, int nparam, const void *dBs, const void *dCs, const void *dHs,
+                              const void *dYs, const void *dDMs, void *dGrad, void *dGradC, void *dLogml, void *dAlpha, void *dBeta,
+                              size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a trend gradient request launches ("" for a request that would be refused). Pure host logic. */
+const char *matinv_trend_grad_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional; hDMs is read only with hGrad). Synchronous. */
+int matinv_trend_grad_batched_host(int dtype, int n, int nbasis, int ntarget, int nparam, const void *hBs, const void *hCs, const void *hHs,
+                                   const void *hYs, const void *hDMs, void *hGrad, void *hGradC, void *hLogml, void *hAlpha, void *hBeta,
+                                   size_t batch, int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
