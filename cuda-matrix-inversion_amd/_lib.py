@@ -53,6 +53,7 @@ NATIVE_NAMES = [
     "matinv_multi_target_grad_batched", "matinv_multi_target_grad_kernel_name", "matinv_multi_target_grad_batched_host",
     "matinv_trend_batched", "matinv_trend_kernel_name", "matinv_trend_batched_host",
     "matinv_trend_grad_batched", "matinv_trend_grad_kernel_name", "matinv_trend_grad_batched_host",
+    "matinv_trend_loo_batched", "matinv_trend_loo_kernel_name", "matinv_trend_loo_batched_host",
 ]
 GJ_NATURAL_FIRST, GJ_PIVOT, GJ_ADAPTIVE = 0, 1, 2
 
@@ -178,6 +179,12 @@ def lib() -> ctypes.CDLL:
     L.matinv_trend_grad_kernel_name.argtypes = [ci, ci]
     L.matinv_trend_grad_batched_host.restype = ci
     L.matinv_trend_grad_batched_host.argtypes = [ci, ci, ci, ci, ci] + [vp] * 10 + [sz, vp]
+    L.matinv_trend_loo_batched.restype = ci
+    L.matinv_trend_loo_batched.argtypes = [ci, ci, ci, ci] + [vp] * 7 + [sz, vp, vp]
+    L.matinv_trend_loo_kernel_name.restype = ctypes.c_char_p
+    L.matinv_trend_loo_kernel_name.argtypes = [ci, ci]
+    L.matinv_trend_loo_batched_host.restype = ci
+    L.matinv_trend_loo_batched_host.argtypes = [ci, ci, ci, ci] + [vp] * 7 + [sz, vp]
     L.matinv_sample_batched.restype = ci
     L.matinv_sample_batched.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
     L.matinv_sample_batched_host.restype = ci

@@ -1397,6 +1397,107 @@ def trend_grad_kernel_name(dtype, n: int) -> str:
     return _lib.lib().matinv_trend_grad_kernel_name(code, n).decode()
 
 
+_TREND_LOO_OUTPUTS = ("mean", "var", "logpl")
+
+
+def _trend_loo_plan(n, batch, want, given, numel, Hs, Ys, nbasis, ntarget):
+    """what a trend leave-one-out request computes and its counts: (asked, nbasis, ntarget, sizes)"""
+    unknown = set(want) - set(_TREND_LOO_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_TREND_LOO_OUTPUTS}")
+    if want is _TREND_LOO_OUTPUTS and Ys is None:  # the default: what the inputs given allow
+        want = ("var",)
+    asked = {k: given[k] is not None or k in want for k in _TREND_LOO_OUTPUTS}
+    if not any(asked.values()):
+        raise ValueError("no output requested")
+    targets = asked["mean"] or asked["logpl"]
+    if Hs is None:
+        raise ValueError("the basis vectors Hs are needed")
+    if targets and Ys is None:
+        raise ValueError("mean and logpl need the targets Ys")
+    if nbasis is None:
+        nbasis = numel(Hs) // (batch * n) if batch else 1
+    if not 1 <= nbasis <= 16 or nbasis >= n:
+        raise ValueError(f"nbasis must be in 1 .. min(16, n - 1) (got {nbasis}): n - 1 points must carry the basis")
+    if not targets:
+        ntarget = 0
+    elif ntarget is None:
+        ntarget = numel(Ys) // (batch * n) if batch else 0
+    if batch and numel(Hs) < batch * nbasis * n:
+        raise ValueError("Hs needs batch*K*n elements")
+    if targets and batch and (ntarget < 1 or numel(Ys) < batch * ntarget * n):
+        raise ValueError("Ys needs batch*D*n elements, D >= 1")
+    sizes = dict(mean=batch * ntarget * n, var=batch * n, logpl=batch * ntarget)
+    return asked, nbasis, ntarget, sizes
+
+
+def trend_loo_batched(n, Bs, Cs, Hs, Ys=None, mean=None, var=None, logpl=None, batchSize=None, info=None, want=_TREND_LOO_OUTPUTS,
+                      nbasis=None, ntarget=None):
+    """Leave-one-out cross-validation of a GP with a linear trend (universal kriging) on device tensors (matinv_trend_loo_batched;
+    asynchronous on torch's current stream): all n held-out predictions of each of the D targets from one factorisation. With
+    M_k = B_k + diag c_k, Kinv = M_k^-1, H the K basis vectors, A = H^T Kinv H, P = Kinv - Kinv H A^-1 H^T Kinv and alpha_t = P y_kt:
+        var[k, i] = 1 / P_ii,  mean[k, t, i] = y_kti - alpha_ti / P_ii,
+        logpl[k, t] = sum_i (1/2 log P_ii - 1/2 alpha_ti^2 / P_ii) - n/2 log 2 pi
+    Hs, Ys as in trend_batched. mean has the layout of Ys, var is batchSize*n, logpl batchSize*D. K and D are inferred from Hs.numel() and
+    Ys.numel() unless `nbasis` / `ntarget` are given; 1 <= K <= min(16, n - 1).
+    An output is computed when its tensor is given or its name is in `want` (then it is allocated); at least one; which are asked for
+    changes no bit of the others. var needs no targets: the default `want` is ("var",) when Ys is None. Cs may be None (M = B). Only B's
+    lower triangle is read and no input is modified. info = the 1-based column of the first non-positive pivot of M, n + b for the first
+    non-positive pivot b of A (both as trend_batched), or n + K + i for the first point i (1-based) whose P_ii is not > 0 (holding it out
+    leaves the basis rank deficient); every requested output of that matrix is then NaN. A tiny positive P_ii is returned as it is.
+    Returns (mean, var, logpl), None for what was not asked for."""
+    import torch
+    _require_cuda(Bs, Cs, Hs, Ys, mean, var, logpl, info)
+    if batchSize is None:
+        batchSize = Bs.numel() // (n * n)
+    given = dict(mean=mean, var=var, logpl=logpl)
+    asked, nbasis, ntarget, sizes = _trend_loo_plan(n, batchSize, want, given, lambda t: t.numel(), Hs, Ys, nbasis, ntarget)
+    for k in _TREND_LOO_OUTPUTS:
+        if asked[k] and given[k] is None:
+            given[k] = torch.empty(sizes[k], dtype=Bs.dtype, device=Bs.device)
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Hs, Ys, *given.values())):
+        raise TypeError("Bs, Cs, Hs, Ys and the outputs must have one dtype")
+    if (Cs is not None and Cs.numel() < batchSize * n) or \
+            any(given[k] is not None and given[k].numel() < sizes[k] for k in _TREND_LOO_OUTPUTS):
+        raise ValueError("Cs and var need batchSize*n elements, mean batchSize*D*n, logpl batchSize*D")
+    _check_info(info, batchSize)
+    targets = asked["mean"] or asked["logpl"]
+    p = _tensor_ptr
+    with torch.cuda.device(Bs.device):
+        _lib.check(_lib.lib().matinv_trend_loo_batched(
+            _torch_dtype_code(Bs), n, nbasis, ntarget, p(Bs), p(Cs), p(Hs), p(Ys) if targets else None,
+            *(p(given[k]) for k in _TREND_LOO_OUTPUTS), batchSize, p(info), _stream_ptr(Bs)))
+    return tuple(given[k] for k in _TREND_LOO_OUTPUTS)
+
+
+def trend_loo_batched_host(n, Bs: np.ndarray, Cs, Hs, Ys=None, want=_TREND_LOO_OUTPUTS, nbasis=None, ntarget=None):
+    """matinv_trend_loo_batched_host on numpy batches (packed; Cs may be None; Ys may be None when only "var" is wanted, which the default
+    `want` then is): returns (mean, var, logpl, info), None for the outputs not in want. Synchronous."""
+    Bs = np.ascontiguousarray(Bs)
+    Cs, Hs, Ys = (None if t is None else np.ascontiguousarray(t) for t in (Cs, Hs, Ys))
+    if any(t is not None and t.dtype != Bs.dtype for t in (Cs, Hs, Ys)):
+        raise TypeError("Bs, Cs, Hs and Ys must have one dtype")
+    batch = Bs.size // (n * n)
+    none = dict.fromkeys(_TREND_LOO_OUTPUTS)
+    asked, nbasis, ntarget, sizes = _trend_loo_plan(n, batch, want, none, lambda a: a.size, Hs, Ys, nbasis, ntarget)
+    if Cs is not None and Cs.size < batch * n:
+        raise ValueError("Cs smaller than batch*n")
+    out = {k: np.empty(sizes[k], dtype=Bs.dtype) if asked[k] else None for k in _TREND_LOO_OUTPUTS}
+    info = np.zeros(batch, dtype=np.int32)
+    targets = asked["mean"] or asked["logpl"]
+    p = _array_ptr
+    _lib.check(_lib.lib().matinv_trend_loo_batched_host(
+        _np_dtype_code(Bs.dtype), n, nbasis, ntarget, p(Bs), p(Cs), p(Hs), p(Ys) if targets else None,
+        *(p(out[k]) for k in _TREND_LOO_OUTPUTS), batch, p(info)))
+    return (*(out[k] for k in _TREND_LOO_OUTPUTS), info)
+
+
+def trend_loo_kernel_name(dtype, n: int) -> str:
+    """matinv_trend_loo_kernel_name: the kernel a trend leave-one-out request launches ("" when the request would be refused)."""
+    code = _dtype_code(dtype)
+    return _lib.lib().matinv_trend_loo_kernel_name(code, n).decode()
+
+
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")
 
 

@@ -1471,6 +1471,57 @@ int trend_grad_host(int n, int nbasis, int ntarget, int nparam, const void *hBs,
     });
 }
 
+// ---- leave-one-out cross-validation of the trend model (matinv_trend_loo_batched) --------------------------------------------------------
+// the checks of trend_check_args, in its order; n <= nbasis leaves no held-out fit; var needs no targets
+int trend_loo_check_args(int dtype, int n, int nbasis, int ntarget, const void *dBs, const void *dHs, const void *dYs, const void *dMean,
+                         const void *dVar, const void *dLogPL, size_t batch)
+{
+    const bool targets = dMean || dLogPL;
+    if (int rc = check_head("n", n, dtype)) return rc;
+    if (nbasis < 1 || nbasis > 16) return fail(MATINV_ERR_ARG, "nbasis must be in 1 .. 16 (got %d)", nbasis);
+    if (nbasis >= n) return fail(MATINV_ERR_ARG, "nbasis=%d leaves no held-out fit at n=%d: n - 1 points cannot carry the basis", nbasis, n);
+    if (batch == 0) return MATINV_OK;
+    if (targets && ntarget < 1) return fail(MATINV_ERR_ARG, "ntarget must be >= 1 with mean or logpl (got %d)", ntarget);
+    if (!dBs || !dHs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!targets && !dVar) return fail(MATINV_ERR_ARG, "no output requested (mean, var and logpl are all null)");
+    if (targets && !dYs) return fail(MATINV_ERR_ARG, "mean or logpl requested without the targets (dYs is null)");
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK && targets) rc = check_count("ntarget", ntarget, "targets");
+    return rc;
+}
+
+// n <= 96: the leave-one-out form of the trend tile kernels. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
+template <class T>
+int trend_loo_dispatch(int n, int nbasis, int ntarget, const void *dBs, const void *dCs, const void *dHs, const void *dYs, void *dMean,
+                       void *dVar, void *dLogPL, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *B = static_cast<const T *>(dBs), *c = static_cast<const T *>(dCs), *h = static_cast<const T *>(dHs);
+    T *mn = static_cast<T *>(dMean), *vr = static_cast<T *>(dVar), *lp = static_cast<T *>(dLogPL);
+    const bool targets = mn || lp;
+    const T *y = targets ? static_cast<const T *>(dYs) : nullptr;  // not read for var
+    const int nd = targets ? ntarget : 0;
+    const hipError_t e = trend_loo_tile_supports(n) ? launch_trend_loo_tile<T>(n, nbasis, nd, B, c, h, y, mn, vr, lp, batch, dInfo, stream)
+                                                    : launch_trend_loo_global<T>(n, nbasis, nd, B, c, h, y, mn, vr, lp, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "trend_loo launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int trend_loo_host(int n, int nbasis, int ntarget, const void *hBs, const void *hCs, const void *hHs, const void *hYs, void *hMean,
+                   void *hVar, void *hLogPL, size_t batch, int *info)
+{
+    const bool targets = hMean || hLogPL;
+    const size_t K = (size_t)nbasis, vec = (size_t)n * batch, mat = vec * n, ts = targets ? batch * (size_t)ntarget : 0;
+    // the targets are read for mean and logpl only
+    const StagedIn in[] = {{hBs, mat}, {hCs, vec}, {hHs, vec * K}, {targets ? hYs : nullptr, ts * n}};
+    const StagedOut out[] = {{hMean, ts * n}, {hVar, vec}, {hLogPL, ts}};
+    return run_staged<T>("trend_loo", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return trend_loo_dispatch<T>(n, nbasis, ntarget, i[0], i[1], i[2], i[3], o[0], o[1], o[2], batch, dInfo, nullptr);
+    });
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -2117,6 +2168,34 @@ int matinv_trend_grad_batched_host(int dtype, int n, int nbasis, int ntarget, in
     return by_dtype(dtype, [&](auto t) {
         return trend_grad_host<decltype(t)>(n, nbasis, ntarget, nparam, hBs, hCs, hHs, hYs, hDMs, hGrad, hGradC, hLogml, hAlpha, hBeta, batch,
                                             info);
+    });
+}
+
+int matinv_trend_loo_batched(int dtype, int n, int nbasis, int ntarget, const void *dBs, const void *dCs, const void *dHs, const void *dYs,
+                             void *dMean, void *dVar, void *dLogPL, size_t batch, int *dInfo, void *stream)
+{
+    int rc = trend_loo_check_args(dtype, n, nbasis, ntarget, dBs, dHs, dYs, dMean, dVar, dLogPL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return by_dtype(dtype, [&](auto t) {
+        return trend_loo_dispatch<decltype(t)>(n, nbasis, ntarget, dBs, dCs, dHs, dYs, dMean, dVar, dLogPL, batch, dInfo, st);
+    });
+}
+
+// "" below n = 2 as well: with nbasis >= 1 no held-out fit exists at n = 1
+const char *matinv_trend_loo_kernel_name(int dtype, int n)
+{
+    if (!has_kernel_name(dtype, n) || n < 2) return "";
+    return trend_loo_tile_supports(n) ? name_trend_loo_tile(dtype == MATINV_F64, n) : name_trend_loo_global(dtype == MATINV_F64);
+}
+
+int matinv_trend_loo_batched_host(int dtype, int n, int nbasis, int ntarget, const void *hBs, const void *hCs, const void *hHs,
+                                  const void *hYs, void *hMean, void *hVar, void *hLogPL, size_t batch, int *info)
+{
+    int rc = trend_loo_check_args(dtype, n, nbasis, ntarget, hBs, hHs, hYs, hMean, hVar, hLogPL, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return trend_loo_host<decltype(t)>(n, nbasis, ntarget, hBs, hCs, hHs, hYs, hMean, hVar, hLogPL, batch, info);
     });
 }
 

@@ -512,6 +512,20 @@ hipError_t launch_trend_grad_global(int n, int nbasis, int ntarget, int nparam, 
                                     const T *dMs, T *grad, T *gradc, T *Lm, T *Al, T *Be, size_t batch, int *info, hipStream_t stream);
 const char *name_trend_grad_global(bool f64);
 
+// Leave-one-out cross-validation of the trend model (matinv_trend_loo_batched): Bs, Cs, Hs, Ys as above; Mn: as Ys, Vr: batch * n,
+// Lp: batch * ntarget. Every output is optional; Ys is read with Mn and Lp only.
+// (a) the leave-one-out form of the trend tile kernels, n <= 96 (trend_loo_tile_kernels.hip, trend_loo_tile_f32_kernels.hip)
+bool trend_loo_tile_supports(int n);
+template <class T>
+hipError_t launch_trend_loo_tile(int n, int nbasis, int ntarget, const T *Bs, const T *Cs, const T *Hs, const T *Ys, T *Mn, T *Vr, T *Lp,
+                                 size_t batch, int *info, hipStream_t stream);
+const char *name_trend_loo_tile(bool f64, int n);
+// (b) the trend leave-one-out form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_trend_loo_global(int n, int nbasis, int ntarget, const T *Bs, const T *Cs, const T *Hs, const T *Ys, T *Mn, T *Vr, T *Lp,
+                                   size_t batch, int *info, hipStream_t stream);
+const char *name_trend_loo_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

@@ -1976,4 +1976,221 @@ const char *name_trend_grad_global(bool f64)
                : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true, true>";
 }
 
+// ---- leave-one-out cross-validation of the trend model, 96 < n <= 1024 (matinv_trend_loo_batched behind trend_loo_tile_impl.hpp) ---------
+// The trend leave-one-out form of matinv_chol_global: one more template argument again ("Leave-one-out cross-validation of the
+// trend model"). The factorisation, the substitutions on [H | Y], A = H^T Kinv H, its factor, beta and alpha are those of the trend form
+// above; Kinv h_b and alpha_t stay in scratch behind the factor. Then L <- L^-1 in place as in the trend gradient form, L_A^-1 column by
+// column, and one thread per point:
+//     P_ii = sum_{k >= i} (L^-1)_ki^2 - sum_b U_ib^2,   U_ib = sum_{b' <= b} (Kinv H)_ib' L_A^-1[b][b']     (k, b, b' ascending)
+// into LDS; the first i with P_ii not > 0 by an atomic minimum. rp = 1 / P_ii is formed the same way wherever it is used:
+//     var_i = rp      mean_ti = y_ti - alpha_ti rp      logpl_t = sum_i (1/2 log P_ii - 1/2 alpha_ti (alpha_ti rp)) - n/2 log 2 pi
+// one thread per point, per (target, point) pair and per target (i ascending). The order of operations of an output knows nothing of D, of
+// the position of its target, or of which outputs are stored. info: gl_chol_factor's column, n + b for pivot b of A (both as the trend
+// form), n + K + i for the first such point i (1-based); every requested output of that matrix is then NaN. Correct first; speed is not a
+// goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x; `per` = n^2 + n (K + D') + K D' elements of workspace each, D' = D
+// when the targets are read.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR, bool WHITEN, bool MULTI, bool MTGRAD, bool TREND,
+          bool TRENDGRAD, bool TRENDLOO>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Bs, const T *Cs, const T *Hs, const T *Ys, int nbasis, int ntarget,
+                                                                 T *Mn, T *Vr, T *Lp, int *info, int n, T *workspace, size_t per, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR && WHITEN && MULTI && MTGRAD && TREND && TRENDGRAD && TRENDLOO,
+                  "the thirteen-argument form is the trend leave-one-out kernel");
+    __shared__ T col[1024];
+    __shared__ T sA[16 * 17], sLi[16 * 17];
+    __shared__ int s_abad, s_pbad;
+    const size_t k_mat = first + blockIdx.x;
+    const T *A = Bs + k_mat * (size_t)n * n;
+    const bool targets = Mn || Lp;  // block-uniform
+    const size_t nn = (size_t)n * n, K = (size_t)nbasis, nd = targets ? (size_t)ntarget : 0;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *V = W + nn;             // Kinv h_b, b < K, then Kinv y_t -> alpha_t
+    T *Bt = V + (K + nd) * n;  // beta_t
+    const int t = threadIdx.x;
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        T v = A[e];
+        if (Cs && r == c) v += Cs[k_mat * n + r];
+        W[e] = v;
+    }
+    if (t == 0) s_pbad = 0x7fffffff;
+    __syncthreads();
+    int bad = gl_chol_factor(W, n, col);
+    if (!bad) {  // block-uniform
+        for (size_t s = t; s < K + nd; s += GL_THREADS) {
+            const T *x = s < K ? Hs + (k_mat * K + s) * n : Ys + (k_mat * nd + (s - K)) * n;
+            T *v = V + s * n;
+            for (int i = 0; i < n; ++i) v[i] = x[i];
+            for (int k = 0; k < n; ++k) {
+                const T *lk = W + (size_t)k * n;
+                const T w = v[k] / lk[k];
+                v[k] = w;
+                for (int i = k + 1; i < n; ++i) v[i] -= lk[i] * w;
+            }
+            for (int k = n - 1; k >= 0; --k) {
+                const T *lk = W + (size_t)k * n;
+                T a = v[k];
+                for (int i = k + 1; i < n; ++i) a -= lk[i] * v[i];
+                v[k] = a / lk[k];
+            }
+        }
+        __syncthreads();  // Kinv [H | Y] is in V
+        for (size_t e = t; e < K * K; e += GL_THREADS) {
+            const size_t b = e / K, b2 = e - b * K;
+            if (b < b2) continue;
+            const T *h = Hs + (k_mat * K + b) * n, *v = V + b2 * n;
+            T a = 0;
+            for (int i = 0; i < n; ++i) a += h[i] * v[i];
+            sA[b * 17 + b2] = a;
+        }
+        __syncthreads();
+        if (t == 0) {  // A = L_A L_A^T in place, 1 / L_bb on the diagonal (the trend form)
+            int abad = 0;
+            for (int j = 0; j < nbasis; ++j) {
+                const T d = sA[j * 17 + j];
+                if (!(d > (T)0) && abad == 0) abad = j + 1;
+                const T rs = (T)1 / sqrt(d);
+                for (int jj = j + 1; jj < nbasis; ++jj) {
+                    const T m = sA[jj * 17 + j] / d;
+                    for (int i = jj; i < nbasis; ++i) sA[i * 17 + jj] -= sA[i * 17 + j] * m;
+                }
+                sA[j * 17 + j] = rs;
+                for (int i = j + 1; i < nbasis; ++i) sA[i * 17 + j] *= rs;
+            }
+            s_abad = abad;
+        }
+        __syncthreads();
+        if (s_abad) bad = n + s_abad;
+    }
+    if (!bad) {  // block-uniform
+        if (t < nbasis) {  // column t of L_A^-1 (the trend form's, for covbeta)
+            for (int i = 0; i < nbasis; ++i) {
+                T s = i == t ? (T)1 : (T)0;
+                for (int k = 0; k < i; ++k) s -= sA[i * 17 + k] * sLi[k * 17 + t];
+                sLi[i * 17 + t] = s * sA[i * 17 + i];
+            }
+        }
+        for (size_t s = t; s < nd; s += GL_THREADS) {  // beta and alpha as in the trend form
+            const T *y = Ys + (k_mat * nd + s) * n;
+            T *v = V + (K + s) * n, *be = Bt + s * K;
+            for (size_t b = 0; b < K; ++b) {
+                const T *kh = V + b * n;
+                T a = 0;
+                for (int i = 0; i < n; ++i) a += kh[i] * y[i];
+                be[b] = a;
+            }
+            for (int i = 0; i < nbasis; ++i) {
+                T a = be[i];
+                for (int k = 0; k < i; ++k) a -= sA[i * 17 + k] * be[k];
+                be[i] = a * sA[i * 17 + i];
+            }
+            for (int i = nbasis - 1; i >= 0; --i) {
+                T a = be[i];
+                for (int k = nbasis - 1; k > i; --k) a -= sA[k * 17 + i] * be[k];
+                be[i] = a * sA[i * 17 + i];
+            }
+            for (size_t b = 0; b < K; ++b) {
+                const T *kh = V + b * n;
+                const T bb = be[b];
+                for (int i = 0; i < n; ++i) v[i] -= kh[i] * bb;
+            }
+        }
+        __syncthreads();  // the factor is no longer needed; L_A^-1 is in sLi
+        for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+            const T ajj = (T)1 / W[(size_t)j * n + j];
+            for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+            __syncthreads();
+            for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+                T s = 0;
+                for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+                W[(size_t)j * n + i] = -s * ajj;
+            }
+            if (t == 0) W[(size_t)j * n + j] = ajj;
+            __syncthreads();
+        }
+        for (int i = t; i < n; i += GL_THREADS) {
+            T kii = 0, uu = 0;
+            for (int k = i; k < n; ++k) kii += W[(size_t)i * n + k] * W[(size_t)i * n + k];
+            for (int b = 0; b < nbasis; ++b) {
+                T s = 0;
+                for (int b2 = 0; b2 <= b; ++b2) s += V[(size_t)b2 * n + i] * sLi[b * 17 + b2];
+                uu += s * s;
+            }
+            const T p = kii - uu;
+            col[i] = p;
+            if (!(p > (T)0)) atomicMin(&s_pbad, i + 1);
+        }
+        __syncthreads();
+        if (s_pbad != 0x7fffffff) bad = n + nbasis + s_pbad;
+    }
+    if (bad) {  // block-uniform
+        if (Mn)
+            for (size_t e = t; e < nd * n; e += GL_THREADS) Mn[k_mat * nd * n + e] = nan_of<T>();
+        if (Vr)
+            for (int i = t; i < n; i += GL_THREADS) Vr[k_mat * n + i] = nan_of<T>();
+        if (Lp)
+            for (size_t s = t; s < nd; s += GL_THREADS) Lp[k_mat * nd + s] = nan_of<T>();
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    if (Vr)
+        for (int i = t; i < n; i += GL_THREADS) Vr[k_mat * n + i] = (T)1 / col[i];
+    if (Mn)
+        for (size_t e = t; e < nd * n; e += GL_THREADS) {
+            const size_t i = e % n;
+            Mn[k_mat * nd * n + e] = Ys[k_mat * nd * n + e] - V[K * n + e] * ((T)1 / col[i]);
+        }
+    if (Lp)
+        for (size_t s = t; s < nd; s += GL_THREADS) {
+            const T *v = V + (K + s) * n;
+            T a = 0;
+            for (int i = 0; i < n; ++i) {
+                const T p = col[i], al = v[i];
+                a += (T)0.5 * log(p) - (T)0.5 * al * (al * ((T)1 / p));
+            }
+            // 1/2 log 2 pi
+            Lp[k_mat * nd + s] = a - (T)n * (T)0.91893853320467274178;
+        }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_trend_loo_global(int n, int nbasis, int ntarget, const T *Bs, const T *Cs, const T *Hs, const T *Ys, T *Mn, T *Vr, T *Lp,
+                                   size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n)) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_trend_global)
+    const size_t nd = (Mn || Lp) ? (size_t)ntarget : 0, K = (size_t)nbasis;
+    const size_t per = (size_t)n * n + (size_t)n * (K + nd) + K * nd;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true, true, true, true, true, true, true>),
+                           dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Bs, Cs, Hs, Ys, nbasis, ntarget, Mn, Vr, Lp, info, n, ws, per,
+                           off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_trend_loo_global<double>(int, int, int, const double *, const double *, const double *, const double *, double *,
+                                                    double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_trend_loo_global<float>(int, int, int, const float *, const float *, const float *, const float *, float *,
+                                                   float *, float *, size_t, int *, hipStream_t);
+
+const char *name_trend_loo_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true, true, true>";
+}
+
 }  // namespace matinv

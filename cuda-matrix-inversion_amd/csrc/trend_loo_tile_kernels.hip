@@ -1,0 +1,24 @@
+// trend_loo_tile_kernels.hip -- fp64 instantiation of the one-wavefront tile kernels of the leave-one-out cross-validation of a GP with a
+// linear trend (trend_loo_tile_impl.hpp) + the helpers
+#include "trend_loo_tile_impl.hpp"
+
+namespace matinv {
+
+// the sizes of the trend forms: one wavefront holds the lower triangle of up to 6 x 6 tiles (n <= 96) in both precisions
+bool trend_loo_tile_supports(int n) { return trend_tile_supports(n); }
+
+template hipError_t launch_trend_loo_tile<double>(int, int, int, const double *, const double *, const double *, const double *, double *,
+                                                  double *, double *, size_t, int *, hipStream_t);
+
+// the trend leave-one-out form of the SPD inversion kernel of the same tile shape: its name with a third to a fourteenth template argument
+const char *name_trend_loo_tile(bool f64, int n)
+{
+    if (!trend_loo_tile_supports(n)) return "";
+    const TileShape s = tile_shape(n);
+    static thread_local char buf[144];
+    snprintf(buf, sizeof buf, "matinv_spd_tile_%s<%d, %s, true, true, true, true, true, true, true, true, true, true, true, true>",
+             f64 ? "f64" : "f32", s.nt, s.full ? "true" : "false");
+    return buf;
+}
+
+}  // namespace matinv

@@ -477,6 +477,40 @@ int matinv_trend_grad_batched_host(int dtype, int n, int nbasis, int ntarget, in
                                    const void *hYs, const void *hDMs, void *hGrad, void *hGradC, void *hLogml, void *hAlpha, void *hBeta,
                                    size_t batch, int *info);
 
+/* Leave-one-out cross-validation of the trend model (universal kriging), device-resident: all n held-out predictions of every target from
+ * one factorisation (Dubrule's identities; Rasmussen & Williams 5.4.2 with the trend's projection). With M_k = B_k + diag(c_k),
+ * Kinv = M_k^-1, H the K = nbasis basis vectors, A = H^T Kinv H, P = Kinv - Kinv H A^-1 H^T Kinv, D = ntarget targets y_kt and
+ * alpha_t = P y_kt:
+ *   var[k*n + i]                = 1 / P_ii                          predictive variance of observation i from the other n - 1 (its noise
+ *                                                                    c_i and the uncertainty of the trend coefficients included)
+ *   mean[(k*ntarget + t)*n + i] = y_ti - alpha_ti / P_ii            predictive mean of target t at point i from the other n - 1
+ *   logpl[k*ntarget + t]        = sum_i (1/2 log P_ii - 1/2 alpha_ti^2 / P_ii) - n/2 log 2 pi     = sum_i log N(y_ti; mean_ti, var_i)
+ * dBs, dCs, dHs, dYs as in matinv_trend_batched (only the lower triangle of B read; dCs may be NULL; basis vector (k, b) at
+ * (k*nbasis + b)*n, target (k, t) at (k*ntarget + t)*n). Every output is optional and at least one is required (all NULL: MATINV_ERR_ARG).
+ * var depends on M and H only: a call with ntarget = 0 and dYs = dMean = dLogPL = NULL is valid and reads no Y; dMean and dLogPL need
+ * ntarget >= 1 and dYs (otherwise MATINV_ERR_ARG). 1 <= nbasis <= 16 and nbasis < n <= 1024: with n <= nbasis no held-out fit exists
+ * (MATINV_ERR_ARG, checked with n and dtype); n > 1024 and ntarget > 1024: MATINV_ERR_UNSUPPORTED, after the pointer checks;
+ * batch < 2^31; batch == 0 is a no-op after the dtype, n and nbasis checks. No input is modified (outputs must not overlap inputs).
+ * No bit of a result depends on the batch, on the grid or on which outputs are requested; for mean and logpl no bit depends on ntarget or
+ * on the other targets; var does not depend on Y at all.
+ * dInfo (optional): 0; or the 1-based column of the first non-positive (or NaN) pivot of M; or n + b for the first non-positive (or NaN)
+ * pivot b of A -- both exactly the values matinv_trend_batched reports for the same B, c, H; or n + nbasis + i for the first point i
+ * (1-based) whose computed P_ii is not > 0 (<= 0 or NaN): holding i out leaves the basis rank deficient (in exact arithmetic e_i lies in
+ * the span of H). On a non-zero info every requested output of that matrix is NaN; there is no fallback launch. A tiny positive P_ii is
+ * returned as it is and gives a huge variance: the caller judges it.
+ * n <= 96: the leave-one-out form of the trend tile sweep: the trend epilogue up to the factor of A, then U = Kinv H L_A^-T on the MFMA
+ * unit and only the diagonal of P, P_ii = Kinv_ii - sum_b U_ib^2 (n^2/2 + n + K n + D n elements read, n + D n + D written). Beyond, to
+ * n = 1024: the trend leave-one-out form of the global-memory Cholesky kernel on a working copy per matrix in library scratch (k-range
+ * chunks under MATINV_BLOCKED_WS_MB); correct first, not fast. Asynchronous, no host synchronisation. */
+int matinv_trend_loo_batched(int dtype, int n, int nbasis, int ntarget, const void *dBs, const void *dCs, const void *dHs, const void *dYs,
+                             void *dMean, void *dVar, void *dLogPL, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function a trend leave-one-out request launches ("" for a request that would be refused: n < 2, n > 1024, an
+ * unknown dtype). Pure host logic. */
+const char *matinv_trend_loo_kernel_name(int dtype, int n);
+/* Host-pointer form (packed; hCs, `info` and each output optional; hYs is read only with hMean or hLogPL). Synchronous. */
+int matinv_trend_loo_batched_host(int dtype, int n, int nbasis, int ntarget, const void *hBs, const void *hCs, const void *hHs,
+                                  const void *hYs, void *hMean, void *hVar, void *hLogPL, size_t batch, int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
