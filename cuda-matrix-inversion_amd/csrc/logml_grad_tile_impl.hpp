@@ -2,8 +2,8 @@
 // of the batched GP log marginal likelihood on the MFMA tile layout, n <= 96. With M = B + diag c (c optional), K = M^-1, alpha = K d and
 // P symmetric derivative matrices dM_p:
 //     grad[p]  = 1/2 sum_ij (alpha_i alpha_j - K_ij) dM_p[i][j]      gradc[i] = 1/2 (alpha_i^2 - K_ii)      alpha[i] = alpha_i
-// The load, the PanelSolve pipeline and the block-step loop are those of loo_tile_body (loo_tile_impl.hpp), which copied them from
-// spd_tile_body (tile_impl.hpp); copied again, so that the inverse and the LOO kernels compile to what they compiled to before. The sweep
+// The load, the PanelSolve pipeline and the block-step loop are spd_load_lower and spd_full_sweep (spd_sweep.hpp), shared with
+// loo_tile_body (loo_tile_impl.hpp) and every later GP tile kernel. The sweep
 // ends with W = -M^-1 in the lower tiles (diagonal tiles complete); the epilogue folds diag W and W d out of the registers as the LOO
 // epilogue does, turns the accumulators into G = alpha alpha^T + W in place and contracts them with the lower tiles of each dM_p
 // streamed from HBM, so neither M nor its inverse is ever stored.
@@ -15,7 +15,7 @@
 #pragma once
 #include <cstdio>
 
-#include "tile_common.hpp"
+#include "spd_sweep.hpp"
 
 namespace matinv {
 
@@ -54,8 +54,6 @@ __device__ __forceinline__ void logml_grad_tile_body(const T *Bs, const T *Cs, c
     typedef TileGeo<T> G;
     typedef typename G::vec4 vec4;
     constexpr int N = 16 * NT;
-    constexpr int NKB = 4 * NT;
-    typedef PanelSolve<NT, true, T> PS;
     const int l = threadIdx.x;
 
     for (unsigned mat = blockIdx.x; mat < batch; mat += gridDim.x) {
@@ -65,104 +63,12 @@ __device__ __forceinline__ void logml_grad_tile_body(const T *Bs, const T *Cs, c
         int q = l >> 4, c = l & 15;
         asm volatile("" : "+v"(q), "+v"(c));  // see matinv_gj_tile_f64
 
-        // W = A^T tile layout, lower tiles only; in the diagonal tiles the strictly upper elements come from their mirror position,
-        // so only the lower triangle of B is ever read (spd_tile_body)
+        // the load and the sweep the GP tile kernels share (spd_sweep.hpp): W = -M^-1 in the lower tiles, diagonal tiles complete
         vec4 acc[NT][NT];
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                if (tj > ti) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 16 * ti + G::trow(r, q), col = 16 * tj + c;
-                    const bool in = FULL || ti < NT - 1 || (row < n && col < n);  // tj <= ti: only the last tile row reaches beyond n
-                    const int hi = row > col ? row : col, lo = row > col ? col : row;
-                    T v = in ? A[(unsigned)(lo * n + hi)] : ((row == col) ? (T)1 : (T)0);
-                    if (Cs && ti == tj && row == col && in) v += Cs[(size_t)mat * n + row];
-                    acc[ti][tj][r] = v;
-                }
-            }
+        spd_load_lower<T, NT, FULL>(acc, A, Cs ? Cs + (size_t)mat * n : nullptr, n, q, c);
         unsigned long long bad = 0;
         int binfo = 0;  // column of the first non-positive pivot + 1
-        T aop[NT], bop[NT];
-
-        spd_panel_to_lds<NT, T>(panel, acc, 0, q, c);
-        wave_lds_sync();
-        {
-            PS ps0;
-            ps0.binfo = &binfo;
-#pragma unroll
-            for (int s = 0; s < PS::NSTAGE; ++s) ps0.stage(s, panel, 0, q, c, aop, bop, bad);
-        }
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            // ragged n: a block step over four columns of identity padding only touches padding -- skipped (as in gj_tile_body)
-            if (!FULL && kb > 4 * (NT - 1) && kb - 4 * (NT - 1) >= G::real_blocks(n - 16 * (NT - 1))) continue;
-            spd_prep_operands<NT, T>(acc, bop, kb, q, c);
-            if (kb + 1 < NKB) {
-                const int tn = (kb + 1) >> 2;
-                // (a) the tiles the next panel is read from: column tn (ti >= tn) and row tn (tj < tn)
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti) {
-                    if (ti < tn) continue;
-                    acc[ti][tn] = G::mfma(aop[ti], bop[tn], acc[ti][tn]);
-                }
-#pragma unroll
-                for (int tj = 0; tj < NT; ++tj) {
-                    if (tj >= tn) continue;
-                    acc[tn][tj] = G::mfma(aop[tn], bop[tj], acc[tn][tj]);
-                }
-                // (b) the other lower tiles, pinned between the pieces of the next panel: 2 MFMAs cover the latency of (a), then the
-                //     panel is staged, then the remaining MFMAs are spread evenly over the solve stages (counters fold to literals)
-                constexpr int NB = NT * (NT + 1) / 2 - NT;
-                constexpr int NS = PS::NSTAGE;
-                T aop_next[NT], bop_next[NT];
-                PS ps;
-                ps.binfo = &binfo;
-                int count = 0, ev = 0;  // MFMAs of (b) issued so far; next event (0 = stage the panel, 1 + s = stage s)
-                auto run_events = [&](bool flush) {
-#pragma unroll
-                    for (int e = 0; e < NS + 1; ++e) {
-                        const int lead = NB < 2 ? NB : 2;
-                        const int thr = (e == 0) ? lead : lead + ((NB - lead) * e) / NS;
-                        if (e == ev && (flush || thr <= count)) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (e == 0) {
-                                wave_lds_sync();
-                                spd_panel_to_lds<NT, T>(panel, acc, kb + 1, q, c);
-                                wave_lds_sync();
-                            } else {
-                                ps.stage(e - 1, panel, kb + 1, q, c, aop_next, bop_next, bad);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            ++ev;
-                        }
-                    }
-                };
-                run_events(false);
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < NT; ++tj) {
-                        if (tj > ti || ti == tn || tj == tn) continue;
-                        acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
-                        ++count;
-                        run_events(false);
-                    }
-                run_events(true);
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti) { aop[ti] = aop_next[ti]; bop[ti] = bop_next[ti]; }
-            } else {
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < NT; ++tj) {
-                        if (tj > ti) continue;
-                        acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
-                    }
-            }
-        }
+        spd_full_sweep<T, NT, FULL>(acc, panel, n, q, c, bad, binfo);
 
         // ---- epilogue: W = -M^-1 in the lower tiles ------------------------------------------------------------------------------
         const T *vd = Ds + (size_t)mat * n;

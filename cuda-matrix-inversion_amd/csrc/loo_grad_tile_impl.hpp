@@ -4,8 +4,10 @@
 //     b_i = alpha_i / kappa_i      beta = K b      s_i = (1 + alpha_i^2 / kappa_i) / kappa_i      H = K diag(s) K
 //     G = 1/2 (alpha beta^T + beta alpha^T) - 1/2 H
 //     grad[p] = sum_ij G_ij dM_p[i][j]      gradc[i] = G_ii      logpl = sum_i (1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i) - n/2 log 2 pi
-// The load, the PanelSolve pipeline and the block-step loop are those of predict_tile_body (predict_tile_impl.hpp), copied once more so
-// that every earlier kernel compiles to what it compiled to before. The sweep ends with W = -M^-1 in the lower tiles (diagonal tiles
+// The load, the PanelSolve pipeline and the block-step loop are spd_load_lower and spd_full_sweep of spd_sweep.hpp, which the other GP
+// tile kernels call, kept HERE as a copy of their own: called from the shared header, the fp32 forms lost the constant offsets of a fifth
+// of their panel stores (one address register per store, 7 to 23 registers more) and the full fp32 6 x 6 form spilled 12 registers to
+// scratch ("The shared SPD sweep"). A change to the sweep is made there and here. The sweep ends with W = -M^-1 in the lower tiles (diagonal tiles
 // complete); the epilogue folds alpha, kappa and beta out of the registers as the gradient epilogue does, builds H one tile column at
 // a time on the MFMA unit as the prediction epilogue builds T = W A, turns that column into G in place and contracts it with the same
 // tiles of each dM_p streamed from HBM. Neither M, its inverse nor H is ever stored.

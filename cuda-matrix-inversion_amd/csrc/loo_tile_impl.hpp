@@ -2,8 +2,10 @@
 // cross-validation of a Gaussian process (Rasmussen & Williams 5.4.2) on the MFMA tile layout, n <= 96. With M = B + diag c
 // (c optional), kappa_i = [M^-1]_ii and alpha = M^-1 d:
 //     mean_i = d_i - alpha_i / kappa_i      var_i = 1 / kappa_i      logpl = sum_i (1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i) - n/2 log(2 pi)
-// The load, the PanelSolve pipeline and the block-step loop are those of spd_tile_body (tile_impl.hpp), copied so that the inverse
-// kernels compile to what they compiled to before: one wavefront per matrix, lower-triangular 16 x 16 accumulator tiles, the next
+// The load, the PanelSolve pipeline and the block-step loop are spd_load_lower and spd_full_sweep of spd_sweep.hpp, which the later GP
+// tile kernels call, kept HERE as a copy of their own: called from the shared header, the ragged fp32 4 x 4 form, which fills its 96
+// registers to the last one, spilled 7 of them to scratch ("The shared SPD sweep"). A change to the sweep is made there and
+// here. One wavefront per matrix, lower-triangular 16 x 16 accumulator tiles, the next
 // block's panel solved between the MFMAs of the current one. The sweep ends with W = -M^-1 in the lower tiles (diagonal tiles
 // complete); the epilogue folds diag W and W d out of the registers, so neither M nor its inverse is ever stored.
 // HBM traffic per matrix: n^2 / 2 + 2 n elements in, 2 n + 1 out.

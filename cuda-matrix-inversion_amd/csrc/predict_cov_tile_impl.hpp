@@ -2,8 +2,10 @@
 // joint predictive covariance between a GP's query points on the MFMA tile layout, n <= 96. With M = B + diag c (c optional), K = M^-1,
 // alpha = K d and Q query points per matrix, a_i the cross-covariance vector of query i and E the Q x Q prior covariance of the queries:
 //     mean[i] = a_i^T alpha      cov[i][j] = E[i][j] - a_i^T K a_j
-// The load, the PanelSolve pipeline, the block-step loop and the alpha step are those of predict_tile_body (predict_tile_impl.hpp), copied
-// once more so that every earlier kernel compiles to what it compiled to before. The sweep ends with W = -M^-1 in the lower tiles; the
+// The load, the PanelSolve pipeline and the block-step loop are spd_load_lower and spd_full_sweep of spd_sweep.hpp, kept HERE as a copy
+// of their own: called from the shared header, the 1 x 1 and 2 x 2 forms came out with other v_cndmask counts ("The shared
+// SPD sweep"). A change to the sweep is made there and here. The alpha step is that of predict_tile_body (predict_tile_impl.hpp). The
+// sweep ends with W = -M^-1 in the lower tiles; the
 // epilogue takes the queries in groups of 16 as the prediction form does, and for every column group g builds T_g = W A_g once and
 // multiplies it with A_g'^T for every row group g' >= g on the MFMA unit: only the lower block triangle is computed, the upper one is a
 // copy of its bits, and neither M nor its inverse is ever stored.

@@ -2,8 +2,8 @@
 // many query points per covariance matrix on the MFMA tile layout, n <= 96. With M = B + diag c (c optional), K = M^-1, alpha = K d and Q
 // query points per matrix, a_j the cross-covariance vector of query j and e_j its prior variance:
 //     mean[j] = a_j^T alpha      var[j] = e_j - a_j^T K a_j
-// The load, the PanelSolve pipeline and the block-step loop are those of logml_grad_tile_body (logml_grad_tile_impl.hpp), copied once
-// more so that the inverse, the LOO and the gradient kernels compile to what they compiled to before. The sweep ends with W = -M^-1 in
+// The load, the PanelSolve pipeline and the block-step loop are spd_load_lower and spd_full_sweep (spd_sweep.hpp), shared with the LOO
+// and the gradient kernels. The sweep ends with W = -M^-1 in
 // the lower tiles (diagonal tiles complete); the epilogue folds alpha = -W d out of the registers as the gradient epilogue does, then
 // takes the queries in groups of 16: a group is an N x 16 right-hand side, so T = W A is MFMA work, and neither M nor its inverse is
 // ever stored.
@@ -45,7 +45,6 @@ __device__ __forceinline__ void predict_tile_body(const T *Bs, const T *Cs, cons
     constexpr int N = 16 * NT;
     constexpr int NKB = 4 * NT;
     constexpr int NS = predict_qstride(N);
-    typedef PanelSolve<NT, true, T> PS;
     const int l = threadIdx.x;
 
     for (unsigned mat = blockIdx.x; mat < batch; mat += gridDim.x) {
@@ -55,104 +54,12 @@ __device__ __forceinline__ void predict_tile_body(const T *Bs, const T *Cs, cons
         int q = l >> 4, c = l & 15;
         asm volatile("" : "+v"(q), "+v"(c));  // see matinv_gj_tile_f64
 
-        // W = A^T tile layout, lower tiles only; in the diagonal tiles the strictly upper elements come from their mirror position,
-        // so only the lower triangle of B is ever read (spd_tile_body)
+        // the load and the sweep the GP tile kernels share (spd_sweep.hpp): W = -M^-1 in the lower tiles, diagonal tiles complete
         vec4 acc[NT][NT];
-#pragma unroll
-        for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < NT; ++tj) {
-                if (tj > ti) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 16 * ti + G::trow(r, q), col = 16 * tj + c;
-                    const bool in = FULL || ti < NT - 1 || (row < n && col < n);  // tj <= ti: only the last tile row reaches beyond n
-                    const int hi = row > col ? row : col, lo = row > col ? col : row;
-                    T v = in ? A[(unsigned)(lo * n + hi)] : ((row == col) ? (T)1 : (T)0);
-                    if (Cs && ti == tj && row == col && in) v += Cs[(size_t)mat * n + row];
-                    acc[ti][tj][r] = v;
-                }
-            }
+        spd_load_lower<T, NT, FULL>(acc, A, Cs ? Cs + (size_t)mat * n : nullptr, n, q, c);
         unsigned long long bad = 0;
         int binfo = 0;  // column of the first non-positive pivot + 1
-        T aop[NT], bop[NT];
-
-        spd_panel_to_lds<NT, T>(panel, acc, 0, q, c);
-        wave_lds_sync();
-        {
-            PS ps0;
-            ps0.binfo = &binfo;
-#pragma unroll
-            for (int s = 0; s < PS::NSTAGE; ++s) ps0.stage(s, panel, 0, q, c, aop, bop, bad);
-        }
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            // ragged n: a block step over four columns of identity padding only touches padding -- skipped (as in gj_tile_body)
-            if (!FULL && kb > 4 * (NT - 1) && kb - 4 * (NT - 1) >= G::real_blocks(n - 16 * (NT - 1))) continue;
-            spd_prep_operands<NT, T>(acc, bop, kb, q, c);
-            if (kb + 1 < NKB) {
-                const int tn = (kb + 1) >> 2;
-                // (a) the tiles the next panel is read from: column tn (ti >= tn) and row tn (tj < tn)
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti) {
-                    if (ti < tn) continue;
-                    acc[ti][tn] = G::mfma(aop[ti], bop[tn], acc[ti][tn]);
-                }
-#pragma unroll
-                for (int tj = 0; tj < NT; ++tj) {
-                    if (tj >= tn) continue;
-                    acc[tn][tj] = G::mfma(aop[tn], bop[tj], acc[tn][tj]);
-                }
-                // (b) the other lower tiles, pinned between the pieces of the next panel: 2 MFMAs cover the latency of (a), then the
-                //     panel is staged, then the remaining MFMAs are spread evenly over the solve stages (counters fold to literals)
-                constexpr int NB = NT * (NT + 1) / 2 - NT;
-                constexpr int NSG = PS::NSTAGE;
-                T aop_next[NT], bop_next[NT];
-                PS ps;
-                ps.binfo = &binfo;
-                int count = 0, ev = 0;  // MFMAs of (b) issued so far; next event (0 = stage the panel, 1 + s = stage s)
-                auto run_events = [&](bool flush) {
-#pragma unroll
-                    for (int e = 0; e < NSG + 1; ++e) {
-                        const int lead = NB < 2 ? NB : 2;
-                        const int thr = (e == 0) ? lead : lead + ((NB - lead) * e) / NSG;
-                        if (e == ev && (flush || thr <= count)) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (e == 0) {
-                                wave_lds_sync();
-                                spd_panel_to_lds<NT, T>(panel, acc, kb + 1, q, c);
-                                wave_lds_sync();
-                            } else {
-                                ps.stage(e - 1, panel, kb + 1, q, c, aop_next, bop_next, bad);
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            ++ev;
-                        }
-                    }
-                };
-                run_events(false);
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < NT; ++tj) {
-                        if (tj > ti || ti == tn || tj == tn) continue;
-                        acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
-                        ++count;
-                        run_events(false);
-                    }
-                run_events(true);
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti) { aop[ti] = aop_next[ti]; bop[ti] = bop_next[ti]; }
-            } else {
-#pragma unroll
-                for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-                    for (int tj = 0; tj < NT; ++tj) {
-                        if (tj > ti) continue;
-                        acc[ti][tj] = G::mfma(aop[ti], bop[tj], acc[ti][tj]);
-                    }
-            }
-        }
+        spd_full_sweep<T, NT, FULL>(acc, panel, n, q, c, bad, binfo);
 
         // ---- epilogue: W = -M^-1 in the lower tiles ------------------------------------------------------------------------------
         const bool ok = bad == 0;

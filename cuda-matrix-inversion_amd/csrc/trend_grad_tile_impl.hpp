@@ -6,7 +6,9 @@
 //     logml_t = -1/2 (y_t^T alpha_t + log det M + log det A + (n - K) log 2 pi)    alpha[t] = alpha_t    beta[t] = A^-1 H^T Kinv y_t
 // the gradient of sum_t logml_t of matinv_trend_batched with respect to the parameter behind dM_p and to c_i (H does not depend on
 // either). The load, the PanelSolve pipeline, the block-step loop and the pivot fold are those of trend_tile_body (trend_tile_impl.hpp),
-// copied once more so that every earlier kernel compiles to what it compiled to before. The sweep ends with W = -Kinv in the lower
+// copied once more so that every earlier kernel compiles to what it compiled to before. A copy of spd_load_lower and
+// spd_full_sweep (spd_sweep.hpp) as it stands: called from the shared header these forms pair their LDS stores differently and spill more
+// SGPRs into VGPR lanes ("The shared SPD sweep"); a change to the sweep is made there and here. The sweep ends with W = -Kinv in the lower
 // tiles. The epilogue has two phases:
 //   1. trend_tile_body's without queries and without covbeta: H staged, T_H = W H parked in hq, A factored by the wave with the quotient
 //      update, L^-1 in a 16 x 17 LDS tile, log det A through a PivotProduct; per group of 16 targets T_g = W Y_g, -beta,

@@ -4,7 +4,9 @@
 // alpha_t = P y_t, Dubrule's identities (the zero-mean formulas of loo_tile_impl.hpp with P in place of Kinv):
 //     var[i] = 1 / P_ii        mean[t][i] = y_ti - alpha_ti / P_ii        logpl[t] = sum_i (1/2 log P_ii - 1/2 alpha_ti^2 / P_ii) - n/2 log 2 pi
 // The load, the PanelSolve pipeline and the block-step loop are those of trend_grad_tile_body (trend_grad_tile_impl.hpp), copied once more
-// so that every earlier kernel compiles to what it compiled to before; the pivot product is left out (no output holds a log-determinant).
+// so that every earlier kernel compiles to what it compiled to before; the pivot product is left out (no output holds a log-determinant). A copy of spd_load_lower and
+// spd_full_sweep (spd_sweep.hpp) as it stands: called from the shared header these forms pair their LDS stores differently and spill more
+// SGPRs into VGPR lanes ("The shared SPD sweep"); a change to the sweep is made there and here.
 // The sweep ends with W = -Kinv in the lower tiles. Phase 1 of trend_grad_tile_body follows without its logml and beta stores: H staged,
 // T_H = W H parked in hq, A factored by the wave with the quotient update, L^-1 in its 16 x 17 LDS tile. Then, new here:
 //   1. U = T_H L^-T on the MFMA unit, 4 MFMAs per tile row (step 2a of trend_grad_tile_body), kept in registers: hq still holds T_H for the

@@ -7,7 +7,9 @@
 //     mean[t][j] = a_j^T alpha_t + g_j^T beta_t
 //     var[j] = e_j - a_j^T Kinv a_j + r_j^T A^-1 r_j,   r_j = g_j - H^T Kinv a_j
 // The load, the PanelSolve pipeline, the block-step loop and the pivot fold are those of multi_target_tile_body
-// (multi_target_tile_impl.hpp), copied once more so that every earlier kernel compiles to what it compiled to before. The sweep ends with
+// (multi_target_tile_impl.hpp), copied once more so that every earlier kernel compiles to what it compiled to before. A copy of spd_load_lower and
+// spd_full_sweep (spd_sweep.hpp) as it stands: called from the shared header these forms pair their LDS stores differently and spill more
+// SGPRs into VGPR lanes ("The shared SPD sweep"); a change to the sweep is made there and here. The sweep ends with
 // W = -Kinv in the lower tiles. What this form adds is the epilogue:
 //   1. H is staged as ONE group of 16 vectors, zero beyond K and beyond n. T_H = W H is built as every T_g is; -A = H^T T_H is one
 //      16 x 16 block in 4 NT MFMAs. A gets an identity diagonal beyond K (its off-diagonal padding is exactly zero: zero operands).
