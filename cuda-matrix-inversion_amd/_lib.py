@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MATINV_LIB", os.path.join(_HERE, "libmatinv_hip.so"))
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_DEVICE = 0, -1, -2, -3, -4
 F64, F32 = 0, 1
 ALGO_GAUSS_JORDAN, ALGO_CHOLESKY = 0, 1
+COV_SE, COV_MATERN52 = 0, 1
 KERNEL_AUTO, KERNEL_LDS, KERNEL_ROWLANE, KERNEL_TILE, KERNEL_ROW, KERNEL_GLOBAL, KERNEL_BLOCKED, KERNEL_TILEP = 0, 1, 2, 3, 4, 5, 6, 7
 
 REFERENCE_GPU_NAMES = [
@@ -54,6 +55,7 @@ NATIVE_NAMES = [
     "matinv_trend_batched", "matinv_trend_kernel_name", "matinv_trend_batched_host",
     "matinv_trend_grad_batched", "matinv_trend_grad_kernel_name", "matinv_trend_grad_batched_host",
     "matinv_trend_loo_batched", "matinv_trend_loo_kernel_name", "matinv_trend_loo_batched_host",
+    "matinv_ard_logml_batched", "matinv_ard_logml_kernel_name", "matinv_ard_logml_batched_host",
 ]
 GJ_NATURAL_FIRST, GJ_PIVOT, GJ_ADAPTIVE = 0, 1, 2
 
@@ -185,6 +187,12 @@ def lib() -> ctypes.CDLL:
     L.matinv_trend_loo_kernel_name.argtypes = [ci, ci]
     L.matinv_trend_loo_batched_host.restype = ci
     L.matinv_trend_loo_batched_host.argtypes = [ci, ci, ci, ci] + [vp] * 7 + [sz, vp]
+    L.matinv_ard_logml_batched.restype = ci
+    L.matinv_ard_logml_batched.argtypes = [ci, ci, ci, ci, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+    L.matinv_ard_logml_kernel_name.restype = ctypes.c_char_p
+    L.matinv_ard_logml_kernel_name.argtypes = [ci, ci, ci]
+    L.matinv_ard_logml_batched_host.restype = ci
+    L.matinv_ard_logml_batched_host.argtypes = [ci, ci, ci, ci, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]
     L.matinv_sample_batched.restype = ci
     L.matinv_sample_batched.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
     L.matinv_sample_batched_host.restype = ci

@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import (GJ_ADAPTIVE, GJ_NATURAL_FIRST, GJ_PIVOT,  # noqa: F401
                    ALGO_CHOLESKY, ALGO_GAUSS_JORDAN, F32, F64, KERNEL_AUTO, KERNEL_BLOCKED, KERNEL_GLOBAL, KERNEL_LDS,  # noqa: F401
-                   KERNEL_ROW, KERNEL_ROWLANE, KERNEL_TILE, KERNEL_TILEP, MatinvError)
+                   KERNEL_ROW, KERNEL_ROWLANE, KERNEL_TILE, KERNEL_TILEP, COV_MATERN52, COV_SE, MatinvError)
 
 
 def _np_dtype_code(dtype) -> int:
@@ -1496,6 +1496,91 @@ def trend_loo_kernel_name(dtype, n: int) -> str:
     """matinv_trend_loo_kernel_name: the kernel a trend leave-one-out request launches ("" when the request would be refused)."""
     code = _dtype_code(dtype)
     return _lib.lib().matinv_trend_loo_kernel_name(code, n).decode()
+
+
+_ARD_OUTPUTS = ("logml", "grad", "alpha")
+
+
+def _ard_plan(n, X, y, theta, ndim, batch, numel):
+    """(ndim, batch, xstride, ystride) of an ARD request: ndim is the last axis of a 2-D or 3-D X unless given, the batch is what theta
+    holds, and an X of n*ndim elements (a y of n) beside a larger batch is ONE shared point set (target vector): stride 0"""
+    if ndim is None:
+        if len(X.shape) < 2:
+            raise ValueError("ndim is needed with a flat X")
+        ndim = int(X.shape[-1])
+    if ndim < 1:
+        raise ValueError(f"ndim must be >= 1 (got {ndim})")
+    if batch is None:
+        batch = numel(theta) // (ndim + 2)
+    if numel(theta) < batch * (ndim + 2):
+        raise ValueError("theta needs batch*(ndim + 2) elements: log sf2, log l_1 .. log l_ndim, log sn2")
+    xstride = 0 if numel(X) == n * ndim and batch > 1 else n * ndim
+    ystride = 0 if numel(y) == n and batch > 1 else n
+    if numel(X) < (batch * n * ndim if xstride else n * ndim) or numel(y) < (batch * n if ystride else n):
+        raise ValueError("X needs batch*n*ndim elements (or n*ndim: one shared point set), y batch*n (or n)")
+    return ndim, batch, xstride, ystride
+
+
+def ard_logml_batched(n, X, y, theta, kind=COV_SE, logml=None, grad=None, alpha=None, ndim=None, batchSize=None, info=None,
+                      want=_ARD_OUTPUTS):
+    """GP log marginal likelihood and its gradient from coordinates on device tensors (matinv_ard_logml_batched; asynchronous on torch's
+    current stream): the covariance matrices are generated inside the kernel and never reach memory. X: the points, point-major
+    (batch, n, ndim) -- or (n, ndim) for one point set shared by the batch; y: (batch, n) or (n,) likewise; theta: (batch, ndim + 2) =
+    (log sf2, log l_1 .. log l_ndim, log sn2) per matrix; kind: COV_SE or COV_MATERN52. A flat X needs ndim. An output is computed when
+    its tensor is given or its name is in `want` (then it is allocated); at least one. Returns (logml, grad, alpha): batch, batch*(ndim+2)
+    and batch*n elements, None for what was not asked for. grad is with respect to theta."""
+    import torch
+    _require_cuda(X, y, theta, logml, grad, alpha, info)
+    unknown = set(want) - set(_ARD_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_ARD_OUTPUTS}")
+    if logml is None and grad is None and alpha is None and not want:
+        raise ValueError("no output requested")
+    ndim, batch, xstride, ystride = _ard_plan(n, X, y, theta, ndim, batchSize, lambda t: t.numel())
+    if logml is None and "logml" in want:
+        logml = torch.empty(batch, dtype=X.dtype, device=X.device)
+    if grad is None and "grad" in want:
+        grad = torch.empty(batch * (ndim + 2), dtype=X.dtype, device=X.device)
+    if alpha is None and "alpha" in want:
+        alpha = torch.empty(batch * n, dtype=X.dtype, device=X.device)
+    if any(t is not None and t.dtype != X.dtype for t in (y, theta, logml, grad, alpha)):
+        raise TypeError("X, y, theta, logml, grad and alpha must have one dtype")
+    if (logml is not None and logml.numel() < batch) or (grad is not None and grad.numel() < batch * (ndim + 2)) or \
+            (alpha is not None and alpha.numel() < batch * n):
+        raise ValueError("logml needs batch elements, grad batch*(ndim + 2), alpha batch*n")
+    _check_info(info, batch)
+    p = _tensor_ptr
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.lib().matinv_ard_logml_batched(
+            _torch_dtype_code(X), kind, n, ndim, p(X), xstride, p(y), ystride, p(theta), p(logml), p(grad), p(alpha), batch, p(info),
+            _stream_ptr(X)))
+    return logml, grad, alpha
+
+
+def ard_logml_batched_host(n, X: np.ndarray, y: np.ndarray, theta: np.ndarray, kind=COV_SE, want=_ARD_OUTPUTS, ndim=None):
+    """matinv_ard_logml_batched_host on numpy arrays (shapes as ard_logml_batched): returns (logml, grad, alpha, info), None for the
+    outputs not in want. Synchronous."""
+    X, y, theta = np.ascontiguousarray(X), np.ascontiguousarray(y), np.ascontiguousarray(theta)
+    if y.dtype != X.dtype or theta.dtype != X.dtype:
+        raise TypeError("X, y and theta must have one dtype")
+    unknown = set(want) - set(_ARD_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_ARD_OUTPUTS}")
+    ndim, batch, xstride, ystride = _ard_plan(n, X, y, theta, ndim, None, lambda a: a.size)
+    logml = np.empty(batch, dtype=X.dtype) if "logml" in want else None
+    grad = np.empty(batch * (ndim + 2), dtype=X.dtype) if "grad" in want else None
+    alpha = np.empty(batch * n, dtype=X.dtype) if "alpha" in want else None
+    info = np.zeros(batch, dtype=np.int32)
+    p = _array_ptr
+    _lib.check(_lib.lib().matinv_ard_logml_batched_host(
+        _np_dtype_code(X.dtype), kind, n, ndim, p(X), xstride, p(y), ystride, p(theta), p(logml), p(grad), p(alpha), batch, p(info)))
+    return logml, grad, alpha, info
+
+
+def ard_logml_kernel_name(dtype, kind: int, n: int) -> str:
+    """matinv_ard_logml_kernel_name: the kernel such a request launches ("" when the request would be refused)."""
+    code = _dtype_code(dtype)
+    return _lib.lib().matinv_ard_logml_kernel_name(code, kind, n).decode()
 
 
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")

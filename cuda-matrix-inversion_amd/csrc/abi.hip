@@ -1522,6 +1522,55 @@ int trend_loo_host(int n, int nbasis, int ntarget, const void *hBs, const void *
     });
 }
 
+// ---- GP log marginal likelihood and its gradient from coordinates (matinv_ard_logml_batched) -------------------------------------------
+// kind and ndim >= 1 are checked with n and dtype, as nbasis is in the trend families; ndim > 16 is a count limit
+int ard_check_args(int dtype, int kind, int n, int ndim, const void *dXs, size_t xstride, const void *dYs, size_t ystride,
+                   const void *dThetas, const void *dLogML, const void *dGrad, const void *dAlpha, size_t batch)
+{
+    if (int rc = check_head("n", n, dtype)) return rc;
+    if (kind != MATINV_COV_SE && kind != MATINV_COV_MATERN52) return fail(MATINV_ERR_ARG, "unknown covariance function %d", kind);
+    if (ndim < 1) return fail(MATINV_ERR_ARG, "ndim must be >= 1 (got %d)", ndim);
+    if (batch == 0) return MATINV_OK;
+    if (xstride != 0 && xstride != (size_t)n * (size_t)ndim)
+        return fail(MATINV_ERR_ARG, "xstride must be n*ndim = %zu, or 0 for one shared point set (got %zu)", (size_t)n * (size_t)ndim, xstride);
+    if (ystride != 0 && ystride != (size_t)n)
+        return fail(MATINV_ERR_ARG, "ystride must be n = %d, or 0 for one shared target vector (got %zu)", n, ystride);
+    if (!dXs || !dYs || !dThetas) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dLogML && !dGrad && !dAlpha) return fail(MATINV_ERR_ARG, "no output requested (logml, grad and alpha are all null)");
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK && ndim > ARD_MAX_DIM)
+        rc = fail(MATINV_ERR_UNSUPPORTED, "ndim=%d exceeds the limit of %d dimensions per point", ndim, ARD_MAX_DIM);
+    return rc;
+}
+
+// n <= 96: the ARD form of the SPD tile kernels. Beyond, to n = 1024: that of the global-memory Cholesky kernel.
+template <class T>
+int ard_dispatch(int kind, int n, int ndim, const void *dXs, size_t xstride, const void *dYs, size_t ystride, const void *dThetas,
+                 void *dLogML, void *dGrad, void *dAlpha, size_t batch, int *dInfo, hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *x = static_cast<const T *>(dXs), *y = static_cast<const T *>(dYs), *th = static_cast<const T *>(dThetas);
+    T *lm = static_cast<T *>(dLogML), *gr = static_cast<T *>(dGrad), *al = static_cast<T *>(dAlpha);
+    const hipError_t e = ard_tile_supports(n) ? launch_ard_tile<T>(kind, n, ndim, x, xstride, y, ystride, th, lm, gr, al, batch, dInfo, stream)
+                                              : launch_ard_global<T>(kind, n, ndim, x, xstride, y, ystride, th, lm, gr, al, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "ard_logml launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int ard_host(int kind, int n, int ndim, const void *hXs, size_t xstride, const void *hYs, size_t ystride, const void *hThetas, void *hLogML,
+             void *hGrad, void *hAlpha, size_t batch, int *info)
+{
+    const size_t pts = (size_t)n * ndim, P = (size_t)ndim + 2;
+    // a shared point set or target vector (stride 0) is staged once, with its own count
+    const StagedIn in[] = {{hXs, xstride ? batch * pts : pts}, {hYs, ystride ? batch * (size_t)n : (size_t)n}, {hThetas, batch * P}};
+    const StagedOut out[] = {{hLogML, batch}, {hGrad, batch * P}, {hAlpha, batch * (size_t)n}};
+    return run_staged<T>("ard_logml", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return ard_dispatch<T>(kind, n, ndim, i[0], xstride, i[1], ystride, i[2], o[0], o[1], o[2], batch, dInfo, nullptr);
+    });
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -2196,6 +2245,34 @@ int matinv_trend_loo_batched_host(int dtype, int n, int nbasis, int ntarget, con
     if (rc != MATINV_OK || batch == 0) return rc;
     return by_dtype(dtype, [&](auto t) {
         return trend_loo_host<decltype(t)>(n, nbasis, ntarget, hBs, hCs, hHs, hYs, hMean, hVar, hLogPL, batch, info);
+    });
+}
+
+int matinv_ard_logml_batched(int dtype, int kind, int n, int ndim, const void *dXs, size_t xstride, const void *dYs, size_t ystride,
+                             const void *dThetas, void *dLogML, void *dGrad, void *dAlpha, size_t batch, int *dInfo, void *stream)
+{
+    int rc = ard_check_args(dtype, kind, n, ndim, dXs, xstride, dYs, ystride, dThetas, dLogML, dGrad, dAlpha, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return by_dtype(dtype, [&](auto t) {
+        return ard_dispatch<decltype(t)>(kind, n, ndim, dXs, xstride, dYs, ystride, dThetas, dLogML, dGrad, dAlpha, batch, dInfo, st);
+    });
+}
+
+// the covariance function is a run-time argument of the kernel: the name depends on it only through "" for an unknown one
+const char *matinv_ard_logml_kernel_name(int dtype, int kind, int n)
+{
+    if (!has_kernel_name(dtype, n) || (kind != MATINV_COV_SE && kind != MATINV_COV_MATERN52)) return "";
+    return ard_tile_supports(n) ? name_ard_tile(dtype == MATINV_F64, n) : name_ard_global(dtype == MATINV_F64);
+}
+
+int matinv_ard_logml_batched_host(int dtype, int kind, int n, int ndim, const void *hXs, size_t xstride, const void *hYs, size_t ystride,
+                                  const void *hThetas, void *hLogML, void *hGrad, void *hAlpha, size_t batch, int *info)
+{
+    int rc = ard_check_args(dtype, kind, n, ndim, hXs, xstride, hYs, ystride, hThetas, hLogML, hGrad, hAlpha, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return ard_host<decltype(t)>(kind, n, ndim, hXs, xstride, hYs, ystride, hThetas, hLogML, hGrad, hAlpha, batch, info);
     });
 }
 

@@ -526,6 +526,23 @@ hipError_t launch_trend_loo_global(int n, int nbasis, int ntarget, const T *Bs, 
                                    size_t batch, int *info, hipStream_t stream);
 const char *name_trend_loo_global(bool f64);
 
+// GP log marginal likelihood and its gradient from coordinates (matinv_ard_logml_batched): Xs: point-major, element (i, k) of matrix b at
+// b * xstride + i * ndim + k (xstride = n * ndim, or 0: one point set for the batch); Ys: b * ystride + i (ystride = n or 0);
+// Th: batch * (ndim + 2) = (log sf2, log l_1 .. log l_ndim, log sn2); kind: MATINV_COV_*. Lm: batch, Gr: batch * (ndim + 2),
+// Al: batch * n; every output is optional. 1 <= ndim <= ARD_MAX_DIM.
+constexpr int ARD_MAX_DIM = 16;
+// (a) the ARD form of the SPD tile kernels, n <= 96 (ard_tile_kernels.hip, ard_tile_f32_kernels.hip)
+bool ard_tile_supports(int n);
+template <class T>
+hipError_t launch_ard_tile(int kind, int n, int ndim, const T *Xs, size_t xstride, const T *Ys, size_t ystride, const T *Th, T *Lm, T *Gr,
+                           T *Al, size_t batch, int *info, hipStream_t stream);
+const char *name_ard_tile(bool f64, int n);
+// (b) the ARD form of the global-memory Cholesky kernel, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_ard_global(int kind, int n, int ndim, const T *Xs, size_t xstride, const T *Ys, size_t ystride, const T *Th, T *Lm, T *Gr,
+                             T *Al, size_t batch, int *info, hipStream_t stream);
+const char *name_ard_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

@@ -7,6 +7,7 @@
 //   matinv_chol_global  Cholesky factor, in-place triangular inverse, L^-T L^-1 (SPD input, lower triangle read).
 // It is a functional path (2 n^3 * sizeof(T) bytes of cache traffic per matrix), not a tuned one: the blocked, MFMA-based
 // large-n path is listed as next in DESIGN.md.
+#include "ard_element.hpp"
 #include "common.hpp"
 #include "pivot_product.hpp"
 
@@ -2191,6 +2192,209 @@ const char *name_trend_loo_global(bool f64)
 {
     return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true, true, true, true, true, true>"
                : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true, true, true>";
+}
+
+// ---- GP log marginal likelihood and its gradient from coordinates, 96 < n <= 1024 (matinv_ard_logml_batched behind ard_tile_impl.hpp) ---
+// The ARD form of matinv_chol_global: one more template argument again ("Hyperparameter fits from coordinates"). The matrix is
+// never read: z = x / l goes to the n ndim elements of scratch behind the working copy (dimension k at Z + k n), and the lower triangle of
+// M = sf2 phi(s) + sn2 I is GENERATED into the working copy with the element function of the tile kernels (ard_element.hpp). It is factored
+// and the factor inverted in place as in the log-marginal-likelihood gradient form; thread 0 folds the diagonal of L into a PivotProduct
+// (logdet = 2 log prod L_ii) before the inversion. Then alpha = L^-T (L^-1 y), y^T alpha on a fixed LDS tree, K over L^-1 one column at
+// a time, and with w = 1/2 on the diagonal and 1 below:
+//     one pass over the lower triangle regenerates s_rc, sums w G_rc sf2 phi into grad[0] and G_rr into grad[ndim + 1] and leaves
+//     w G_rc sf2 psi(s_rc) in place of K_rc; one pass per dimension k sums W_rc (z_rk - z_ck)^2.
+// Every sum is per thread in element order, then on a fixed LDS tree. Not SPD: info = the failing column + 1 and every requested output
+// NaN. Correct first; speed is not a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x; per = n^2 + n ndim elements of
+// workspace each.
+template <class T, bool LOO, bool GRAD, bool PREDICT, bool COV, bool LOOGRAD, bool COLOUR, bool WHITEN, bool MULTI, bool MTGRAD, bool TREND,
+          bool TRENDGRAD, bool TRENDLOO, bool ARD>
+__global__ __launch_bounds__(GL_THREADS) void matinv_chol_global(const T *Xs, size_t xstride, const T *Ys, size_t ystride, const T *Th,
+                                                                 int ndim, int kind, T *Lm, T *Gr, T *Al, int *info, int n, T *workspace,
+                                                                 size_t per, size_t first)
+{
+    static_assert(LOO && GRAD && PREDICT && COV && LOOGRAD && COLOUR && WHITEN && MULTI && MTGRAD && TREND && TRENDGRAD && TRENDLOO && ARD,
+                  "the fourteen-argument form is the ARD log-marginal-likelihood kernel");
+    __shared__ T col[1024], va[1024], vy[1024];
+    __shared__ T s_ld;
+    const size_t k_mat = first + blockIdx.x;
+    const int t = threadIdx.x;
+    const size_t nn = (size_t)n * n;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *Z = W + nn;
+    const T *th = Th + k_mat * (size_t)(ndim + 2);
+    const T sf2 = ard_exp(th[0]), sn2 = ard_exp(th[ndim + 1]);
+    T *const gm = Gr ? Gr + k_mat * (size_t)(ndim + 2) : nullptr;
+    if (t < ndim) col[t] = ard_exp(th[1 + t]);
+    __syncthreads();
+    {
+        const T *X = Xs + k_mat * xstride, *Y = Ys + k_mat * ystride;
+        for (int e = t; e < n * ndim; e += GL_THREADS) {
+            const int i = e / ndim, k = e - i * ndim;
+            Z[(size_t)k * n + i] = X[e] / col[k];
+        }
+        for (int i = t; i < n; i += GL_THREADS) va[i] = Y[i];
+    }
+    __syncthreads();
+    // s_rc in the order k = 0 .. ndim - 1
+    auto sqdist = [&](int r, int c) {
+        T s = 0;
+        for (int k = 0; k < ndim; ++k) {
+            const T d = Z[(size_t)k * n + r] - Z[(size_t)k * n + c];
+            s = ard_fma(d, d, s);
+        }
+        return s;
+    };
+    // block sum on a fixed tree; every thread returns with the sum
+    auto block_sum = [&](T v) {
+        __syncthreads();
+        col[t] = v;
+        __syncthreads();
+        for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+            if (t < off) col[t] += col[t + off];
+            __syncthreads();
+        }
+        return col[0];
+    };
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        W[e] = ard_m(sqdist(r, c), kind, sf2, sn2, r == c);
+    }
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        if (Al)
+            for (int i = t; i < n; i += GL_THREADS) Al[k_mat * n + i] = nan_of<T>();
+        if (gm)
+            for (int p = t; p < ndim + 2; p += GL_THREADS) gm[p] = nan_of<T>();
+        if (t == 0) {
+            if (Lm) Lm[k_mat] = nan_of<T>();
+            if (info) info[k_mat] = bad;
+        }
+        return;
+    }
+    if (t == 0) {
+        PivotProduct<T> prod;
+        for (int i = 0; i < n; ++i) prod.fold(W[(size_t)i * n + i]);
+        s_ld = (T)2 * prod.log_value();
+    }
+    for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+        const T ajj = (T)1 / W[(size_t)j * n + j];
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+        __syncthreads();
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+            W[(size_t)j * n + i] = -s * ajj;
+        }
+        if (t == 0) W[(size_t)j * n + j] = ajj;
+        __syncthreads();
+    }
+    // y = L^-1 d: (L^-1)_kj sits at W[j*n + k]
+    for (int k = t; k < n; k += GL_THREADS) {
+        T s = 0;
+        for (int j = 0; j <= k; ++j) s += W[(size_t)j * n + k] * va[j];
+        vy[k] = s;
+    }
+    __syncthreads();
+    // alpha_i = column i of L^-1 against y; it takes the place of y once y_i alpha_i is taken
+    T qpart = 0;
+    for (int i = t; i < n; i += GL_THREADS) {
+        T a = 0;
+        for (int k = i; k < n; ++k) a += W[(size_t)i * n + k] * vy[k];
+        qpart += va[i] * a;
+        va[i] = a;
+        if (Al) Al[k_mat * n + i] = a;
+    }
+    const T quad = block_sum(qpart);
+    // log 2 pi
+    if (Lm && t == 0) Lm[k_mat] = (T)-0.5 * ((quad + s_ld) + (T)n * (T)1.83787706640934548356);
+    if (gm) {  // block-uniform
+        __syncthreads();
+        // column c of K over column c of L^-1; the columns beyond c are still those of L^-1
+        for (int c = 0; c < n; ++c) {
+            for (int k = c + t; k < n; k += GL_THREADS) col[k] = W[(size_t)c * n + k];
+            __syncthreads();
+            for (int r = c + t; r < n; r += GL_THREADS) {
+                T s = 0;
+                if (r == c) {
+                    for (int k = r; k < n; ++k) s += col[k] * col[k];
+                } else {
+                    for (int k = r; k < n; ++k) s += W[(size_t)r * n + k] * col[k];
+                }
+                W[(size_t)c * n + r] = s;
+            }
+            __syncthreads();
+        }
+        T p0 = 0, pn = 0;
+        for (size_t e = t; e < nn; e += GL_THREADS) {
+            const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+            if (r < c) continue;
+            T phi, psi;
+            ard_element(sqdist(r, c), kind, phi, psi);
+            const T g = va[r] * va[c] - W[e];
+            const T wg = (r == c ? (T)0.5 : (T)1) * g;
+            if (r == c) pn += g;
+            p0 += wg * (sf2 * phi);
+            W[e] = wg * (sf2 * psi);
+        }
+        const T s0 = block_sum(p0);
+        const T sn = block_sum(pn);
+        if (t == 0) {
+            gm[0] = s0;
+            gm[ndim + 1] = ((T)0.5 * sn2) * sn;
+        }
+        for (int k = 0; k < ndim; ++k) {
+            const T *zk = Z + (size_t)k * n;
+            T s = 0;
+            for (size_t e = t; e < nn; e += GL_THREADS) {
+                const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+                if (r < c) continue;
+                const T d = zk[r] - zk[c];
+                s += W[e] * (d * d);
+            }
+            const T sk = block_sum(s);
+            if (t == 0) gm[1 + k] = sk;
+        }
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_ard_global(int kind, int n, int ndim, const T *Xs, size_t xstride, const T *Ys, size_t ystride, const T *Th, T *Lm, T *Gr,
+                             T *Al, size_t batch, int *info, hipStream_t stream)
+{
+    if (!global_family_supports<T>(n) || ndim < 1 || ndim > ARD_MAX_DIM) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_logml_grad_global)
+    const size_t per = (size_t)n * n + (size_t)n * ndim;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_chol_global<T, true, true, true, true, true, true, true, true, true, true, true, true, true>),
+                           dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Xs, xstride, Ys, ystride, Th, ndim, kind, Lm, Gr, Al, info, n, ws,
+                           per, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_ard_global<double>(int, int, int, const double *, size_t, const double *, size_t, const double *, double *, double *,
+                                              double *, size_t, int *, hipStream_t);
+template hipError_t launch_ard_global<float>(int, int, int, const float *, size_t, const float *, size_t, const float *, float *, float *,
+                                             float *, size_t, int *, hipStream_t);
+
+const char *name_ard_global(bool f64)
+{
+    return f64 ? "matinv_chol_global<double, true, true, true, true, true, true, true, true, true, true, true, true, true>"
+               : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true, true, true, true>";
 }
 
 }  // namespace matinv

@@ -2,7 +2,8 @@
 // per matrix, lower-triangular 16 x 16 accumulator tiles, the next block's panel solved between the MFMAs of the current one; the sweep
 // ends with W = -M^-1 in the lower tiles (diagonal tiles complete). The order of operations is that of spd_tile_body (tile_impl.hpp),
 // plus PanelSolve::binfo.
-// CALLED by logml_grad_tile_body, predict_tile_body and multi_target_tile_body.
+// CALLED by logml_grad_tile_body, predict_tile_body, multi_target_tile_body and (the sweep only: its tiles are generated, not loaded)
+// ard_tile_body.
 // COPIED, line for line, in loo_tile_impl.hpp, loo_grad_tile_impl.hpp, predict_cov_tile_impl.hpp, multi_target_grad_tile_impl.hpp,
 // trend_tile_impl.hpp, trend_grad_tile_impl.hpp and trend_loo_tile_impl.hpp, whose kernels did not compile to the same work (or the
 // same speed) when they called this header: A CHANGE TO THE SWEEP HAS TO BE MADE HERE AND IN THOSE SEVEN FILES, or the outputs that

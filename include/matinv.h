@@ -511,6 +511,43 @@ const char *matinv_trend_loo_kernel_name(int dtype, int n);
 int matinv_trend_loo_batched_host(int dtype, int n, int nbasis, int ntarget, const void *hBs, const void *hCs, const void *hHs,
                                   const void *hYs, void *hMean, void *hVar, void *hLogPL, size_t batch, int *info);
 
+/* GP log marginal likelihood and its gradient FROM COORDINATES, device-resident: the covariance matrix of every batch member is generated
+ * inside the kernel from its n points in ndim dimensions and its ndim + 2 hyperparameters; neither it, nor its inverse, nor a derivative
+ * matrix reaches memory. Per matrix k: points x_i (element (i, d) at dXs[k*xstride + i*ndim + d]), targets y (dYs[k*ystride + i]) and
+ * theta = (log sf2, log l_1 .. log l_ndim, log sn2) at dThetas[k*(ndim + 2)]. With z_id = x_id / l_d and s_ij = sum_d (z_id - z_jd)^2,
+ * summed in the order d = 0 .. ndim - 1:
+ *   M_ij = sf2 phi(s_ij) + sn2 delta_ij        K = M^-1,  alpha = K y,  G = alpha alpha^T - K
+ *   MATINV_COV_SE:        phi(s) = exp(-s/2)                                      psi(s) = phi(s)
+ *   MATINV_COV_MATERN52:  phi(s) = (1 + sqrt5 r + 5 s / 3) exp(-sqrt5 r), r = sqrt s   psi(s) = 5/3 (1 + sqrt5 r) exp(-sqrt5 r)
+ *   logml[k]                  = -1/2 y^T alpha - 1/2 log det M - n/2 log 2 pi
+ *   grad[k*(ndim+2)]          = 1/2 sum_ij G_ij sf2 phi(s_ij)                           d logml / d log sf2
+ *   grad[k*(ndim+2) + 1 + d]  = 1/2 sum_ij G_ij sf2 psi(s_ij) (z_id - z_jd)^2           d logml / d log l_d       (psi = -2 phi')
+ *   grad[k*(ndim+2) + ndim+1] = 1/2 sn2 sum_i G_ii                                      d logml / d log sn2
+ *   alpha[k*n + i]            = alpha_i
+ * xstride is n*ndim, or 0 for one point set shared by the whole batch; ystride is n, or 0 likewise; any other stride: MATINV_ERR_ARG.
+ * dThetas is always per matrix. dLogML: batch, dGrad: batch*(ndim + 2), dAlpha: batch*n elements; each may be NULL (all three NULL:
+ * MATINV_ERR_ARG), and which of them are requested does not change a bit of the others. The result for matrix k depends on matrix k's
+ * inputs alone: no bit depends on the batch, the grid or the strides. 1 <= n <= 1024; 1 <= ndim <= 16 (0 or less: MATINV_ERR_ARG, beyond 16:
+ * MATINV_ERR_UNSUPPORTED); batch < 2^31; batch == 0 is a no-op after the dtype, n, kind and ndim checks. No input is modified.
+ * dInfo (optional): 0, or the 1-based column of the first non-positive (or NaN) leading pivot of M in natural order; every requested
+ * output of that matrix is then NaN. There is no fallback launch.
+ * n <= 96: the ARD form of the one-wavefront SPD tile sweep: every lane generates the accumulator elements it owns from z in LDS, the
+ * epilogue regenerates them once more for the contraction (n ndim + n + ndim + 2 elements read, ndim + 3 + n written). Beyond, to
+ * n = 1024: the ARD form of the global-memory Cholesky kernel, which generates into its working copy in library scratch (k-range chunks
+ * under MATINV_BLOCKED_WS_MB); correct first, not fast. Asynchronous, no host synchronisation. */
+enum {
+    MATINV_COV_SE = 0,       /* squared exponential with one length scale per dimension */
+    MATINV_COV_MATERN52 = 1  /* Matern 5/2, likewise */
+};
+int matinv_ard_logml_batched(int dtype, int kind, int n, int ndim, const void *dXs, size_t xstride, const void *dYs, size_t ystride,
+                             const void *dThetas, void *dLogML, void *dGrad, void *dAlpha, size_t batch, int *dInfo, void *stream);
+/* Name of the __global__ function such a request launches ("" for a request that would be refused: n < 1, n > 1024, an unknown dtype or
+ * kind). Pure host logic. */
+const char *matinv_ard_logml_kernel_name(int dtype, int kind, int n);
+/* Host-pointer form (`info` and each output optional; a shared point set or target vector, stride 0, is staged once). Synchronous. */
+int matinv_ard_logml_batched_host(int dtype, int kind, int n, int ndim, const void *hXs, size_t xstride, const void *hYs, size_t ystride,
+                                  const void *hThetas, void *hLogML, void *hGrad, void *hAlpha, size_t batch, int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
