@@ -56,6 +56,7 @@ NATIVE_NAMES = [
     "matinv_trend_grad_batched", "matinv_trend_grad_kernel_name", "matinv_trend_grad_batched_host",
     "matinv_trend_loo_batched", "matinv_trend_loo_kernel_name", "matinv_trend_loo_batched_host",
     "matinv_ard_logml_batched", "matinv_ard_logml_kernel_name", "matinv_ard_logml_batched_host",
+    "matinv_ard_predict_batched", "matinv_ard_predict_kernel_name", "matinv_ard_predict_batched_host",
 ]
 GJ_NATURAL_FIRST, GJ_PIVOT, GJ_ADAPTIVE = 0, 1, 2
 
@@ -193,6 +194,12 @@ def lib() -> ctypes.CDLL:
     L.matinv_ard_logml_kernel_name.argtypes = [ci, ci, ci]
     L.matinv_ard_logml_batched_host.restype = ci
     L.matinv_ard_logml_batched_host.argtypes = [ci, ci, ci, ci, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp]
+    L.matinv_ard_predict_batched.restype = ci
+    L.matinv_ard_predict_batched.argtypes = [ci, ci, ci, ci, ci, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp]
+    L.matinv_ard_predict_kernel_name.restype = ctypes.c_char_p
+    L.matinv_ard_predict_kernel_name.argtypes = [ci, ci, ci]
+    L.matinv_ard_predict_batched_host.restype = ci
+    L.matinv_ard_predict_batched_host.argtypes = [ci, ci, ci, ci, ci, vp, sz, vp, sz, vp, vp, sz, vp, vp, sz, vp]
     L.matinv_sample_batched.restype = ci
     L.matinv_sample_batched.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
     L.matinv_sample_batched_host.restype = ci

@@ -1501,9 +1501,12 @@ def trend_loo_kernel_name(dtype, n: int) -> str:
 _ARD_OUTPUTS = ("logml", "grad", "alpha")
 
 
-def _ard_plan(n, X, y, theta, ndim, batch, numel):
+def _ard_plan(n, X, y, theta, ndim, batch, numel, Xq=None):
     """(ndim, batch, xstride, ystride) of an ARD request: ndim is the last axis of a 2-D or 3-D X unless given, the batch is what theta
-    holds, and an X of n*ndim elements (a y of n) beside a larger batch is ONE shared point set (target vector): stride 0"""
+    holds, and an X of n*ndim elements (a y of n) beside a larger batch is ONE shared point set (target vector): stride 0.
+    With Xq (a prediction request) the tuple goes on with (nquery, xqstride) by the same rule: Xq is (batch, nquery, ndim) or
+    (nquery, ndim), nquery its last axis but one, and an Xq of nquery*ndim elements beside a larger batch is ONE shared query set. y may
+    then be None (no mean; ystride n)."""
     if ndim is None:
         if len(X.shape) < 2:
             raise ValueError("ndim is needed with a flat X")
@@ -1515,10 +1518,18 @@ def _ard_plan(n, X, y, theta, ndim, batch, numel):
     if numel(theta) < batch * (ndim + 2):
         raise ValueError("theta needs batch*(ndim + 2) elements: log sf2, log l_1 .. log l_ndim, log sn2")
     xstride = 0 if numel(X) == n * ndim and batch > 1 else n * ndim
-    ystride = 0 if numel(y) == n and batch > 1 else n
-    if numel(X) < (batch * n * ndim if xstride else n * ndim) or numel(y) < (batch * n if ystride else n):
+    ystride = 0 if y is not None and numel(y) == n and batch > 1 else n
+    if numel(X) < (batch * n * ndim if xstride else n * ndim) or (y is not None and numel(y) < (batch * n if ystride else n)):
         raise ValueError("X needs batch*n*ndim elements (or n*ndim: one shared point set), y batch*n (or n)")
-    return ndim, batch, xstride, ystride
+    if Xq is None:
+        return ndim, batch, xstride, ystride
+    if len(Xq.shape) < 2 or int(Xq.shape[-1]) != ndim or int(Xq.shape[-2]) < 1:
+        raise ValueError("Xq must be (batch, nquery, ndim), or (nquery, ndim) for one shared query set, with nquery >= 1")
+    nquery = int(Xq.shape[-2])
+    xqstride = 0 if numel(Xq) == nquery * ndim and batch > 1 else nquery * ndim
+    if numel(Xq) < (batch * nquery * ndim if xqstride else nquery * ndim):
+        raise ValueError("Xq needs batch*nquery*ndim elements (or nquery*ndim: one shared query set)")
+    return ndim, batch, xstride, ystride, nquery, xqstride
 
 
 def ard_logml_batched(n, X, y, theta, kind=COV_SE, logml=None, grad=None, alpha=None, ndim=None, batchSize=None, info=None,
@@ -1581,6 +1592,73 @@ def ard_logml_kernel_name(dtype, kind: int, n: int) -> str:
     """matinv_ard_logml_kernel_name: the kernel such a request launches ("" when the request would be refused)."""
     code = _dtype_code(dtype)
     return _lib.lib().matinv_ard_logml_kernel_name(code, kind, n).decode()
+
+
+_ARD_PREDICT_OUTPUTS = ("mean", "var")
+
+
+def ard_predict_batched(n, X, y, theta, Xq, kind=COV_SE, mean=None, var=None, ndim=None, batchSize=None, info=None,
+                        want=_ARD_PREDICT_OUTPUTS):
+    """GP prediction from coordinates on device tensors (matinv_ard_predict_batched; asynchronous on torch's current stream): the
+    covariance matrices and the cross-covariance vectors of the queries are generated inside the kernel and never reach memory. X, y,
+    theta, kind as in ard_logml_batched; Xq: the query points, (batch, nquery, ndim) -- or (nquery, ndim) for one query set shared by
+    the batch; nquery comes from it. An output is computed when its tensor is given or its name is in `want` (then it is allocated); at
+    least one. y may be None when mean is not asked for. Returns (mean, var): batch*nquery elements each, None for what was not asked
+    for. var is the variance of the latent function: add exp(theta[:, ndim + 1]) for that of a noisy observation."""
+    import torch
+    _require_cuda(X, y, theta, Xq, mean, var, info)
+    unknown = set(want) - set(_ARD_PREDICT_OUTPUTS)
+    if unknown:
+        raise ValueError(f"want holds {sorted(unknown)}; the outputs are {_ARD_PREDICT_OUTPUTS}")
+    if mean is None and var is None and not want:
+        raise ValueError("no output requested")
+    ndim, batch, xstride, ystride, nquery, xqstride = _ard_plan(n, X, y, theta, ndim, batchSize, lambda t: t.numel(), Xq)
+    if mean is None and "mean" in want:
+        mean = torch.empty(batch * nquery, dtype=X.dtype, device=X.device)
+    if var is None and "var" in want:
+        var = torch.empty(batch * nquery, dtype=X.dtype, device=X.device)
+    if mean is not None and y is None:
+        raise ValueError("mean needs y")
+    if any(t is not None and t.dtype != X.dtype for t in (y, theta, Xq, mean, var)):
+        raise TypeError("X, y, theta, Xq, mean and var must have one dtype")
+    if any(t is not None and t.numel() < batch * nquery for t in (mean, var)):
+        raise ValueError("mean and var need batch*nquery elements")
+    _check_info(info, batch)
+    p = _tensor_ptr
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.lib().matinv_ard_predict_batched(
+            _torch_dtype_code(X), kind, n, ndim, nquery, p(X), xstride, p(y), ystride, p(theta), p(Xq), xqstride, p(mean), p(var), batch,
+            p(info), _stream_ptr(X)))
+    return mean, var
+
+
+def ard_predict_batched_host(n, X: np.ndarray, y, theta: np.ndarray, Xq: np.ndarray, kind=COV_SE, want=_ARD_PREDICT_OUTPUTS, ndim=None):
+    """matinv_ard_predict_batched_host on numpy arrays (shapes as ard_predict_batched): returns (mean, var, info), None for the outputs
+    not in want. Synchronous."""
+    X, theta, Xq = np.ascontiguousarray(X), np.ascontiguousarray(theta), np.ascontiguousarray(Xq)
+    y = None if y is None else np.ascontiguousarray(y)
+    if theta.dtype != X.dtype or Xq.dtype != X.dtype or (y is not None and y.dtype != X.dtype):
+        raise TypeError("X, y, theta and Xq must have one dtype")
+    unknown = set(want) - set(_ARD_PREDICT_OUTPUTS)
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {_ARD_PREDICT_OUTPUTS}")
+    if "mean" in want and y is None:
+        raise ValueError("mean needs y")
+    ndim, batch, xstride, ystride, nquery, xqstride = _ard_plan(n, X, y, theta, ndim, None, lambda a: a.size, Xq)
+    mean = np.empty(batch * nquery, dtype=X.dtype) if "mean" in want else None
+    var = np.empty(batch * nquery, dtype=X.dtype) if "var" in want else None
+    info = np.zeros(batch, dtype=np.int32)
+    p = _array_ptr
+    _lib.check(_lib.lib().matinv_ard_predict_batched_host(
+        _np_dtype_code(X.dtype), kind, n, ndim, nquery, p(X), xstride, p(y), ystride, p(theta), p(Xq), xqstride, p(mean), p(var), batch,
+        p(info)))
+    return mean, var, info
+
+
+def ard_predict_kernel_name(dtype, kind: int, n: int) -> str:
+    """matinv_ard_predict_kernel_name: the kernel such a request launches ("" when the request would be refused)."""
+    code = _dtype_code(dtype)
+    return _lib.lib().matinv_ard_predict_kernel_name(code, kind, n).decode()
 
 
 _SAMPLE_OUTPUTS = ("Y", "mean", "cov")

@@ -1571,6 +1571,68 @@ int ard_host(int kind, int n, int ndim, const void *hXs, size_t xstride, const v
     });
 }
 
+// ---- GP prediction from coordinates (matinv_ard_predict_batched) ------------------------------------------------------------------------
+// the order of ard_check_args; nquery before the strides, the outputs as predict_check_args words them
+int ard_predict_check_args(int dtype, int kind, int n, int ndim, int nquery, const void *dXs, size_t xstride, const void *dYs, size_t ystride,
+                           const void *dThetas, const void *dXqs, size_t xqstride, const void *dMean, const void *dVar, size_t batch)
+{
+    if (int rc = check_head("n", n, dtype)) return rc;
+    if (kind != MATINV_COV_SE && kind != MATINV_COV_MATERN52) return fail(MATINV_ERR_ARG, "unknown covariance function %d", kind);
+    if (ndim < 1) return fail(MATINV_ERR_ARG, "ndim must be >= 1 (got %d)", ndim);
+    if (batch == 0) return MATINV_OK;
+    if (nquery < 1) return fail(MATINV_ERR_ARG, "nquery must be >= 1 (got %d)", nquery);
+    if (xstride != 0 && xstride != (size_t)n * (size_t)ndim)
+        return fail(MATINV_ERR_ARG, "xstride must be n*ndim = %zu, or 0 for one shared point set (got %zu)", (size_t)n * (size_t)ndim, xstride);
+    if (ystride != 0 && ystride != (size_t)n)
+        return fail(MATINV_ERR_ARG, "ystride must be n = %d, or 0 for one shared target vector (got %zu)", n, ystride);
+    if (xqstride != 0 && xqstride != (size_t)nquery * (size_t)ndim)
+        return fail(MATINV_ERR_ARG, "xqstride must be nquery*ndim = %zu, or 0 for one shared query set (got %zu)",
+                    (size_t)nquery * (size_t)ndim, xqstride);
+    if (!dXs || !dThetas || !dXqs) return fail(MATINV_ERR_ARG, "null device pointer");
+    if (!dMean && !dVar) return fail(MATINV_ERR_ARG, "no output requested (mean and var are both null)");
+    if (dMean && !dYs) return fail(MATINV_ERR_ARG, "mean requested without the observations (dYs is null)");
+    int rc = check_tail("n", n, batch);
+    if (rc == MATINV_OK && ndim > ARD_MAX_DIM)
+        rc = fail(MATINV_ERR_UNSUPPORTED, "ndim=%d exceeds the limit of %d dimensions per point", ndim, ARD_MAX_DIM);
+    return rc;
+}
+
+// n <= 96: the ARD prediction form of the tile kernels. Beyond, to n = 1024: that of the global-memory kernel.
+template <class T>
+int ard_predict_dispatch(int kind, int n, int ndim, int nquery, const void *dXs, size_t xstride, const void *dYs, size_t ystride,
+                         const void *dThetas, const void *dXqs, size_t xqstride, void *dMean, void *dVar, size_t batch, int *dInfo,
+                         hipStream_t stream)
+{
+    int rc = check_device();
+    if (rc) return rc;
+    const T *x = static_cast<const T *>(dXs), *y = static_cast<const T *>(dYs), *th = static_cast<const T *>(dThetas);
+    const T *xq = static_cast<const T *>(dXqs);
+    T *mean = static_cast<T *>(dMean), *var = static_cast<T *>(dVar);
+    const hipError_t e =
+        ard_predict_tile_supports(n)
+            ? launch_ard_predict_tile<T>(kind, n, ndim, nquery, x, xstride, y, ystride, th, xq, xqstride, mean, var, batch, dInfo, stream)
+            : launch_ard_predict_global<T>(kind, n, ndim, nquery, x, xstride, y, ystride, th, xq, xqstride, mean, var, batch, dInfo, stream);
+    if (e != hipSuccess) return fail_hip(e, "ard_predict launch");
+    return MATINV_OK;
+}
+
+template <class T>
+int ard_predict_host(int kind, int n, int ndim, int nquery, const void *hXs, size_t xstride, const void *hYs, size_t ystride,
+                     const void *hThetas, const void *hXqs, size_t xqstride, void *hMean, void *hVar, size_t batch, int *info)
+{
+    const size_t pts = (size_t)n * ndim, qpts = (size_t)nquery * ndim, P = (size_t)ndim + 2, qs = batch * (size_t)nquery;
+    // a shared point set, target vector or query set (stride 0) is staged once, with its own count; the targets are read for mean only
+    const StagedIn in[] = {{hXs, xstride ? batch * pts : pts},
+                           {hMean ? hYs : nullptr, ystride ? batch * (size_t)n : (size_t)n},
+                           {hThetas, batch * P},
+                           {hXqs, xqstride ? batch * qpts : qpts}};
+    const StagedOut out[] = {{hMean, qs}, {hVar, qs}};
+    return run_staged<T>("ard_predict", in, out, batch, info, [&](T *const *i, T *const *o, int *dInfo) {
+        return ard_predict_dispatch<T>(kind, n, ndim, nquery, i[0], xstride, i[1], ystride, i[2], i[3], xqstride, o[0], o[1], batch, dInfo,
+                                       nullptr);
+    });
+}
+
 // ---- batched joint posterior samples at the query points of a GP (matinv_sample_batched) -----------------------------------------------
 int sample_check_args(int dtype, int n, int nquery, int nsample, const void *dBs, const void *dDs, const void *dAs, const void *dZs,
                       const void *dY, const void *dMean, size_t batch)
@@ -2273,6 +2335,38 @@ int matinv_ard_logml_batched_host(int dtype, int kind, int n, int ndim, const vo
     if (rc != MATINV_OK || batch == 0) return rc;
     return by_dtype(dtype, [&](auto t) {
         return ard_host<decltype(t)>(kind, n, ndim, hXs, xstride, hYs, ystride, hThetas, hLogML, hGrad, hAlpha, batch, info);
+    });
+}
+
+int matinv_ard_predict_batched(int dtype, int kind, int n, int ndim, int nquery, const void *dXs, size_t xstride, const void *dYs,
+                               size_t ystride, const void *dThetas, const void *dXqs, size_t xqstride, void *dMean, void *dVar, size_t batch,
+                               int *dInfo, void *stream)
+{
+    int rc = ard_predict_check_args(dtype, kind, n, ndim, nquery, dXs, xstride, dYs, ystride, dThetas, dXqs, xqstride, dMean, dVar, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return by_dtype(dtype, [&](auto t) {
+        return ard_predict_dispatch<decltype(t)>(kind, n, ndim, nquery, dXs, xstride, dYs, ystride, dThetas, dXqs, xqstride, dMean, dVar,
+                                                 batch, dInfo, st);
+    });
+}
+
+// as matinv_ard_logml_kernel_name: the covariance function is a run-time argument of the kernel
+const char *matinv_ard_predict_kernel_name(int dtype, int kind, int n)
+{
+    if (!has_kernel_name(dtype, n) || (kind != MATINV_COV_SE && kind != MATINV_COV_MATERN52)) return "";
+    return ard_predict_tile_supports(n) ? name_ard_predict_tile(dtype == MATINV_F64, n) : name_ard_predict_global(dtype == MATINV_F64);
+}
+
+int matinv_ard_predict_batched_host(int dtype, int kind, int n, int ndim, int nquery, const void *hXs, size_t xstride, const void *hYs,
+                                    size_t ystride, const void *hThetas, const void *hXqs, size_t xqstride, void *hMean, void *hVar,
+                                    size_t batch, int *info)
+{
+    int rc = ard_predict_check_args(dtype, kind, n, ndim, nquery, hXs, xstride, hYs, ystride, hThetas, hXqs, xqstride, hMean, hVar, batch);
+    if (rc != MATINV_OK || batch == 0) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return ard_predict_host<decltype(t)>(kind, n, ndim, nquery, hXs, xstride, hYs, ystride, hThetas, hXqs, xqstride, hMean, hVar, batch,
+                                             info);
     });
 }
 

@@ -543,6 +543,22 @@ hipError_t launch_ard_global(int kind, int n, int ndim, const T *Xs, size_t xstr
                              T *Al, size_t batch, int *info, hipStream_t stream);
 const char *name_ard_global(bool f64);
 
+// GP prediction from coordinates (matinv_ard_predict_batched): Xs, Ys, Th, kind as above; Xqs: query j's coordinate k of matrix b at
+// b * xqstride + j * ndim + k (xqstride = nquery * ndim, or 0: one query set for the batch). mean, var: batch * nquery, each optional;
+// Ys is read with mean only.
+// (a) the ARD prediction form of the bordered log-determinant tile kernels, n <= 96 (ard_predict_tile_kernels.hip, ..._f32_kernels.hip)
+bool ard_predict_tile_supports(int n);
+template <class T>
+hipError_t launch_ard_predict_tile(int kind, int n, int ndim, int nquery, const T *Xs, size_t xstride, const T *Ys, size_t ystride,
+                                   const T *Th, const T *Xqs, size_t xqstride, T *mean, T *var, size_t batch, int *info, hipStream_t stream);
+const char *name_ard_predict_tile(bool f64, int n);
+// (b) the ARD prediction form of the global-memory log-determinant kernel's name, n <= 1024 (global_kernels.hip)
+template <class T>
+hipError_t launch_ard_predict_global(int kind, int n, int ndim, int nquery, const T *Xs, size_t xstride, const T *Ys, size_t ystride,
+                                     const T *Th, const T *Xqs, size_t xqstride, T *mean, T *var, size_t batch, int *info,
+                                     hipStream_t stream);
+const char *name_ard_predict_global(bool f64);
+
 const char *name_gj_lds(bool f64);
 const char *name_chol_lds(bool f64);
 

@@ -2397,4 +2397,170 @@ const char *name_ard_global(bool f64)
                : "matinv_chol_global<float, true, true, true, true, true, true, true, true, true, true, true, true, true>";
 }
 
+// ---- GP prediction from coordinates, 96 < n <= 1024 (matinv_ard_predict_batched behind ard_predict_tile_impl.hpp) ------------------------
+// Two forms above joined: the generation of the ARD form into the working copy (z behind it in scratch, dimension k at Z + k n), then the
+// back end of the prediction form -- factor, L <- L^-1 in place, alpha (with mean only), and one query after the other:
+//     a_j[i] = sf2 phi(sum_k (z_ik - zq_jk)^2) with the element function of the tile kernels, zq_j = xq_j / l in LDS,
+//     v = L^-1 a_j,   var_j = sf2 - sum_k v_k^2,   mean_j = sum_k a_jk alpha_k      (both on the fixed LDS tree)
+// in an order that knows nothing of Q. Not SPD: info = the failing column + 1 and every requested output NaN. Correct first; speed is not
+// a goal here. Workgroup blockIdx.x serves matrix first + blockIdx.x; per = n^2 + n ndim elements of workspace each.
+// The name is matinv_logdet_global's with a third template argument, not one more argument of matinv_chol_global ("Prediction
+// from coordinates", says why).
+template <class T, bool SPD, bool ARDPREDICT>
+__global__ __launch_bounds__(GL_THREADS) void matinv_logdet_global(const T *Xs, size_t xstride, const T *Ys, size_t ystride, const T *Th,
+                                                                   const T *Xqs, size_t xqstride, int nquery, int ndim, int kind, T *mean,
+                                                                   T *var, int *info, int n, T *workspace, size_t per, size_t first)
+{
+    static_assert(SPD && ARDPREDICT, "the three-argument form is the prediction-from-coordinates kernel");
+    __shared__ T col[1024], va[1024], vy[1024], vq[1024];
+    __shared__ T ell[ARD_MAX_DIM], zq[ARD_MAX_DIM];
+    const size_t k_mat = first + blockIdx.x;
+    const int t = threadIdx.x;
+    const size_t nn = (size_t)n * n;
+    T *W = workspace + (size_t)blockIdx.x * per;
+    T *Z = W + nn;
+    const T *th = Th + k_mat * (size_t)(ndim + 2);
+    const T sf2 = ard_exp(th[0]), sn2 = ard_exp(th[ndim + 1]);
+    if (t < ndim) ell[t] = ard_exp(th[1 + t]);
+    __syncthreads();
+    {
+        const T *X = Xs + k_mat * xstride;
+        for (int e = t; e < n * ndim; e += GL_THREADS) {
+            const int i = e / ndim, k = e - i * ndim;
+            Z[(size_t)k * n + i] = X[e] / ell[k];
+        }
+        if (mean) {  // block-uniform: y is read for alpha only
+            const T *Y = Ys + k_mat * ystride;
+            for (int i = t; i < n; i += GL_THREADS) va[i] = Y[i];
+        }
+    }
+    __syncthreads();
+    // s_rc in the order k = 0 .. ndim - 1
+    auto sqdist = [&](int r, int c) {
+        T s = 0;
+        for (int k = 0; k < ndim; ++k) {
+            const T d = Z[(size_t)k * n + r] - Z[(size_t)k * n + c];
+            s = ard_fma(d, d, s);
+        }
+        return s;
+    };
+    // column-major: element (r, c) at c*n + r; the lower triangle only (r >= c)
+    for (size_t e = t; e < nn; e += GL_THREADS) {
+        const int c = (int)(e / n), r = (int)(e - (size_t)c * n);
+        if (r < c) continue;
+        W[e] = ard_m(sqdist(r, c), kind, sf2, sn2, r == c);
+    }
+    __syncthreads();
+    const int bad = gl_chol_factor(W, n, col);
+    if (bad) {  // block-uniform
+        for (int j = t; j < nquery; j += GL_THREADS) {
+            if (mean) mean[k_mat * nquery + j] = nan_of<T>();
+            if (var) var[k_mat * nquery + j] = nan_of<T>();
+        }
+        if (info && t == 0) info[k_mat] = bad;
+        return;
+    }
+    for (int j = n - 1; j >= 0; --j) {  // L <- L^-1 in place, last column first (the loop of the inverse kernel)
+        const T ajj = (T)1 / W[(size_t)j * n + j];
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) col[i] = W[(size_t)j * n + i];
+        __syncthreads();
+        for (int i = j + 1 + t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = j + 1; k <= i; ++k) s += W[(size_t)k * n + i] * col[k];
+            W[(size_t)j * n + i] = -s * ajj;
+        }
+        if (t == 0) W[(size_t)j * n + j] = ajj;
+        __syncthreads();
+    }
+    if (mean) {  // block-uniform
+        // y = L^-1 d: (L^-1)_kj sits at W[j*n + k]
+        for (int k = t; k < n; k += GL_THREADS) {
+            T s = 0;
+            for (int j = 0; j <= k; ++j) s += W[(size_t)j * n + k] * va[j];
+            vy[k] = s;
+        }
+        __syncthreads();
+        // alpha_i = column i of L^-1 against y; it takes the place of y
+        for (int i = t; i < n; i += GL_THREADS) {
+            T a = 0;
+            for (int k = i; k < n; ++k) a += W[(size_t)i * n + k] * vy[k];
+            va[i] = a;
+        }
+        __syncthreads();
+    }
+    const T *Xq = Xqs + k_mat * xqstride;
+    for (int j = 0; j < nquery; ++j) {
+        const size_t out = k_mat * nquery + j;
+        if (t < ndim) zq[t] = Xq[(size_t)j * ndim + t] / ell[t];
+        __syncthreads();
+        for (int i = t; i < n; i += GL_THREADS) {
+            T s = 0;
+            for (int k = 0; k < ndim; ++k) {
+                const T d = Z[(size_t)k * n + i] - zq[k];
+                s = ard_fma(d, d, s);
+            }
+            vq[i] = ard_m(s, kind, sf2, sn2, false);
+        }
+        __syncthreads();
+        T sq = 0, sm = 0;
+        for (int k = t; k < n; k += GL_THREADS) {
+            if (var) {  // v_k = row k of L^-1 against a
+                T s = 0;
+                for (int i = 0; i <= k; ++i) s += W[(size_t)i * n + k] * vq[i];
+                sq += s * s;
+            }
+            if (mean) sm += vq[k] * va[k];
+        }
+        // block sums on a fixed tree
+        col[t] = sq;
+        vy[t] = sm;
+        __syncthreads();
+        for (int off = GL_THREADS / 2; off >= 1; off >>= 1) {
+            if (t < off) {
+                col[t] += col[t + off];
+                vy[t] += vy[t + off];
+            }
+            __syncthreads();
+        }
+        if (t == 0) {
+            if (var) var[out] = sf2 - col[0];
+            if (mean) mean[out] = vy[0];
+        }
+        __syncthreads();  // the next query overwrites zq, vq, col and vy
+    }
+    if (info && t == 0) info[k_mat] = 0;
+}
+
+template <class T>
+hipError_t launch_ard_predict_global(int kind, int n, int ndim, int nquery, const T *Xs, size_t xstride, const T *Ys, size_t ystride,
+                                     const T *Th, const T *Xqs, size_t xqstride, T *mean, T *var, size_t batch, int *info,
+                                     hipStream_t stream)
+{
+    if (!global_family_supports<T>(n) || ndim < 1 || ndim > ARD_MAX_DIM || nquery < 1) return hipErrorInvalidValue;
+    if (batch == 0) return hipSuccess;
+    // the working copies of a k-range chunk fit the blocked-path workspace cap (launch_ard_global)
+    const size_t per = (size_t)n * n + (size_t)n * ndim;
+    size_t chunk = blocked_workspace_cap() / (per * sizeof(T));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    T *ws = nullptr;
+    hipError_t e = scratch_alloc(reinterpret_cast<void **>(&ws), chunk * per * sizeof(T), stream);
+    if (e != hipSuccess) return e;
+    for (size_t off = 0; off < batch && e == hipSuccess; off += chunk) {
+        const size_t cnt = batch - off < chunk ? batch - off : chunk;
+        hipLaunchKernelGGL((matinv_logdet_global<T, true, true>), dim3((unsigned)cnt), dim3(GL_THREADS), 0, stream, Xs, xstride, Ys, ystride,
+                           Th, Xqs, xqstride, nquery, ndim, kind, mean, var, info, n, ws, per, off);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = scratch_free(ws, stream);
+    return e != hipSuccess ? e : e2;
+}
+
+template hipError_t launch_ard_predict_global<double>(int, int, int, int, const double *, size_t, const double *, size_t, const double *,
+                                                      const double *, size_t, double *, double *, size_t, int *, hipStream_t);
+template hipError_t launch_ard_predict_global<float>(int, int, int, int, const float *, size_t, const float *, size_t, const float *,
+                                                     const float *, size_t, float *, float *, size_t, int *, hipStream_t);
+
+const char *name_ard_predict_global(bool f64) { return f64 ? "matinv_logdet_global<double, true, true>" : "matinv_logdet_global<float, true, true>"; }
+
 }  // namespace matinv

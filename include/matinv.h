@@ -548,6 +548,44 @@ const char *matinv_ard_logml_kernel_name(int dtype, int kind, int n);
 int matinv_ard_logml_batched_host(int dtype, int kind, int n, int ndim, const void *hXs, size_t xstride, const void *hYs, size_t ystride,
                                   const void *hThetas, void *hLogML, void *hGrad, void *hAlpha, size_t batch, int *info);
 
+/* GP prediction FROM COORDINATES, device-resident: the counterpart of matinv_ard_logml_batched once theta is fitted. The covariance
+ * matrix of every batch member AND the cross-covariance vectors of its nquery query points are generated inside the kernel; neither they
+ * nor the inverse reach memory. Per matrix k: X, y, theta, z = x / l, s, phi and M = sf2 phi(s) + sn2 I exactly as
+ * matinv_ard_logml_batched defines them, K = M^-1, alpha = K y; query j's coordinate d at dXqs[k*xqstride + j*ndim + d], zq_jd =
+ * xq_jd / l_d:
+ *   a_j[i]               = sf2 phi(sum_d (z_id - zq_jd)^2)        summed in the order d = 0 .. ndim - 1
+ *   mean[k*nquery + j]   = a_j^T alpha
+ *   var[k*nquery + j]    = sf2 - a_j^T K a_j
+ * var is the variance of the LATENT function; the variance of a noisy observation is var + exp(theta[ndim + 1]), which the caller adds.
+ * var is not clamped: where rounding outweighs a tiny variance it can come out slightly negative. A query that coincides with a
+ * training point has s = 0 and a_j[i] = sf2 phi(0) exactly (no noise term: sn2 belongs to M's diagonal alone).
+ * xstride and ystride as in matinv_ard_logml_batched; xqstride is nquery*ndim, or 0 for one query set shared by the whole batch; any
+ * other stride: MATINV_ERR_ARG. dThetas is always per matrix. dMean, dVar: batch*nquery elements; each may be NULL (both NULL:
+ * MATINV_ERR_ARG), and which of them are requested does not change a bit of the other. dYs is read with dMean only and may be NULL
+ * without it (dMean without dYs: MATINV_ERR_ARG). The result for matrix k depends on matrix k's inputs alone: no bit depends on the
+ * batch, the grid or the strides; query j's result does not depend on nquery, on the other queries or on its position among them.
+ * nquery >= 1 (MATINV_ERR_ARG otherwise; no upper limit); 1 <= n <= 1024; 1 <= ndim <= 16 (0 or less: MATINV_ERR_ARG, beyond 16:
+ * MATINV_ERR_UNSUPPORTED); batch < 2^31; batch == 0 is a no-op after the dtype, n, kind and ndim checks. No input is modified.
+ * dInfo (optional): 0, or the 1-based column of the first non-positive (or NaN) leading pivot of M in natural order -- the value
+ * matinv_ard_logml_batched reports for the same X, theta; every requested output of that matrix is then NaN. There is no fallback
+ * launch. A NaN in a QUERY's coordinates makes that query's outputs NaN and changes neither info nor a bit of any other query.
+ * n <= 96: the ARD prediction form of the one-wavefront tile sweep: generation and sweep of the ARD form, then the queries in groups of
+ * 16 whose cross-covariance block is generated in LDS and multiplied on the MFMA unit (n ndim + n + ndim + 2 + nquery ndim elements
+ * read, 2 nquery written). Beyond, to n = 1024: a global-memory Cholesky kernel that generates into its working copy in library scratch
+ * (k-range chunks under MATINV_BLOCKED_WS_MB) and takes one query at a time; correct first, not fast. Asynchronous, no host
+ * synchronisation. */
+int matinv_ard_predict_batched(int dtype, int kind, int n, int ndim, int nquery, const void *dXs, size_t xstride, const void *dYs,
+                               size_t ystride, const void *dThetas, const void *dXqs, size_t xqstride, void *dMean, void *dVar, size_t batch,
+                               int *dInfo, void *stream);
+/* Name of the __global__ function such a request launches ("" for a request that would be refused: n < 1, n > 1024, an unknown dtype or
+ * kind). Pure host logic. */
+const char *matinv_ard_predict_kernel_name(int dtype, int kind, int n);
+/* Host-pointer form (`info` and each output optional; a shared point set, target vector or query set, stride 0, is staged once; hYs is
+ * read only with hMean). Synchronous. */
+int matinv_ard_predict_batched_host(int dtype, int kind, int n, int ndim, int nquery, const void *hXs, size_t xstride, const void *hYs,
+                                    size_t ystride, const void *hThetas, const void *hXqs, size_t xqstride, void *hMean, void *hVar,
+                                    size_t batch, int *info);
+
 /* Joint posterior samples of a GP at its query points, device-resident: with mean_k and cov_k as matinv_predict_cov_batched returns them
  * for the same dBs, dCs, dDs, dAs, dEs,
  *   Y_k[:, s] = mean_k + chol(cov_k) z_ks      dZs, dY: batch*nquery*nsample elements, laid out as in matinv_colour_batched
